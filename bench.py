@@ -721,6 +721,8 @@ def bench_infer(args, rank, world, dev, dist):
     hot.join()
     barrier()
     dt, timer, (mask, npeaks) = timed(args.steps)
+    if args.dump_outputs and rank == 0 and not args.sub_config:          # outside the timed region, before anything reuses the buffers
+        dump_outputs(args.dump_outputs, {"peak_mask": mask, "npeaks": npeaks})
     other = None
     if net is not None and world == 1 and not args.sub_config and not args.no_extras:   # the other arithmetic, same run, for the record (not the headline)
         net.precision = 1 - net.precision
@@ -903,6 +905,35 @@ def bench_launch_check(args, rank, world, dist):
             out["configs"][name] = {"skipped": skipped} if skipped else dict(skel, scaling=kw["scaling"], clips_per_gpu_per_step=per_rank,
                                                                             clips_per_step_all_gpus=per_rank * world)
     return out
+
+
+DUMP_BYTES = 64_000_000     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as <out_dir>/<name>.npy -- float64 for float64
+    and 32/64-bit integer outputs (held exactly), float32 otherwise.  While the set is over DUMP_BYTES, its largest array keeps a fixed,
+    seeded sample of its leading-axis rows (the same rows for the same shape), and the row indices go beside it as <name>_rows.npy."""
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        wide = a.dtype == np.float64 or (np.issubdtype(a.dtype, np.integer) and a.dtype.itemsize >= 4)
+        host[name] = a.astype(np.float64 if wide else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    for name in sorted(host, key=lambda k: -host[k].nbytes):
+        a = host[name]
+        if total <= DUMP_BYTES or a.ndim == 0:
+            break
+        n = a.shape[0]
+        keep = (DUMP_BYTES - (total - a.nbytes) - 8 * n) // (a.nbytes // n)
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: {name} {a.shape} leaves no room under {DUMP_BYTES} bytes")
+        rows = np.sort(np.random.default_rng(0).choice(n, size=min(keep, n), replace=False))
+        host[name], host[name + "_rows"] = a[rows], rows.astype(np.float64)
+        total += host[name].nbytes + host[name + "_rows"].nbytes - a.nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _timer_every(args):
@@ -1197,6 +1228,9 @@ def build_parser():
     ap.add_argument("--dist-strong-global", type=int, default=128, help="global batch of the nested strong-scaled train step (the reference's BATCH_SIZE, training/parameters.py:18): 128 / 64 / 32 / 16 clips per GPU at N = 1 / 2 / 4 / 8; carried by the N = 1 line too (the curve's origin)")
     ap.add_argument("--dist-train-steps", type=int, default=8, help="N > 1 infer line: timed steps of each nested train-step entry")
     ap.add_argument("--dist-train-seconds", type=float, default=8.0, help="N > 1 infer line: clip length of the nested train step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="infer mode: after the timed steps, write what the timed chain returned in its last step (peak masks, peak "
+                         "counts; rank 0) as DIR/<name>.npy, at most 64 MB in all (a fixed, seeded sample of clips beyond that)")
     ap.add_argument("--lib", default=None, help="experiments only: bind another build of the library (e.g. musicfpaugment_amd/libmfpa_exp.so)")
     return ap
 
@@ -1204,6 +1238,10 @@ def build_parser():
 def main():
     args = build_parser().parse_args()
     args.sub_config = False
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.mode != "infer":
+        raise SystemExit("--dump-outputs: infer mode only (the headline chain)")
     if args.lib:
         from musicfpaugment_amd import _lib
         _lib.set_library_path(args.lib)

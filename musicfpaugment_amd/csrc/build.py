@@ -6,6 +6,7 @@ without a GPU; the resulting musicfpaugment_amd/libmfpa.so travels to the GPU bo
 from __future__ import annotations
 
 import hashlib
+import json
 import os
 import shutil
 import subprocess
@@ -15,6 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libmfpa.so")
+RECORD = os.path.join(PKG, "libmfpa.build.json")     # identity of the library in the tree (git-ignored like the library itself)
 OBJ = os.path.join(HERE, "build")
 ARCH = "gfx950"
 
@@ -87,11 +89,19 @@ def build(force: bool = False, verbose: bool = True, experiments: bool = False, 
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    if OUT == globals()["OUT"]:
+        write_record(record(OUT))
     return OUT
 
 
+def write_record(rec: dict) -> None:
+    with open(RECORD, "w") as fh:
+        fh.write(json.dumps(rec, indent=1, sort_keys=True) + "\n")
+
+
 def record(path: str = None) -> dict:
-    """Identity of a built library: sha256, size, hipcc version, flags (written to profiles/BUILD_rNN.txt by __graft_entry__.build())."""
+    """Identity of a built library: sha256, size, hipcc version, flags (build() writes it to RECORD; a round's final one is committed as
+    profiles/BUILD_rNN.txt)."""
     path = path or OUT
     h = hashlib.sha256()
     with open(path, "rb") as fh:

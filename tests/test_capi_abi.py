@@ -148,19 +148,24 @@ def test_product_package_never_imports_the_oracle():
 
 
 def test_committed_build_record_matches_the_sources_in_the_tree():
-    """profiles/BUILD_rNN.txt (written by __graft_entry__.build()) must describe THESE sources: `sources_sha256` covers every .hip / .h of
-    csrc/ and include/mfpa.h.  A record committed before the round's last source change fails here (round 5's was one commit stale)."""
+    """profiles/BUILD_rNN.txt (the round's final build record, committed) must describe THESE sources: `sources_sha256` covers every
+    .hip / .h of csrc/ and include/mfpa.h.  A record committed before the round's last source change fails here (round 5's was one
+    commit stale).  The library in the tree must be the one its own record (written by the build, git-ignored) describes, built from
+    these same sources."""
     import json
     import __graft_entry__ as ge
     from musicfpaugment_amd.csrc import build as b
     path = os.path.join(ROOT, "profiles", ge.BUILD_RECORD)
-    assert os.path.exists(path), f"{path}: run __graft_entry__.build() and commit the record"
+    assert os.path.exists(path), f"{path}: commit the round's final build record"
     rec = json.load(open(path))
     h = hashlib.sha256()
     for f in b._sources() + sorted(x for x in os.listdir(b.HERE) if x.endswith(".h")) + ["../../include/mfpa.h"]:
         with open(os.path.join(b.HERE, f), "rb") as fh:
             h.update(f.encode() + b"\0" + fh.read())
-    assert rec["sources_sha256"] == h.hexdigest(), "profiles/%s is stale: rebuild (python -c 'import __graft_entry__ as g; g.build()') and commit it" % ge.BUILD_RECORD
+    assert rec["sources_sha256"] == h.hexdigest(), "profiles/%s is stale: copy %s over it after a build and commit it" % (ge.BUILD_RECORD, b.RECORD)
     if os.path.exists(b.OUT):                                        # the library in the tree (git-ignored, travels to the GPU box) is the recorded one
+        assert os.path.exists(b.RECORD), f"{b.OUT} has no build record: rebuild (python -c 'import __graft_entry__ as g; g.build()')"
+        local = json.load(open(b.RECORD))
         lib_h = hashlib.sha256(open(b.OUT, "rb").read()).hexdigest()
-        assert rec["sha256"] == lib_h, "libmfpa.so in the tree is not the build the record describes"
+        assert local["sha256"] == lib_h, "libmfpa.so in the tree is not the build the record describes"
+        assert local["sources_sha256"] == h.hexdigest(), "libmfpa.so in the tree was built from other sources: rebuild"

@@ -208,6 +208,36 @@ int mfpa_dejavu_hashes(const uint8_t* mask, int B, int F, int T, int cap, int pe
                        int max_dt, uint8_t* digests, int32_t* t1, int32_t* counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Audfprint hash table and matcher (identification-rate experiment, testing/audfprint_exps.py:17-84).  Integer only, except
+ * the weighted count rawcount / hashesperid (one float64 division).  The table is (2^hashbits, depth) uint32 of
+ * ((id + 1) << timebits) | (time & (2^timebits - 1)); counts (2^hashbits) int32; hashesperid (n_ids) int32.
+ *
+ * mfpa_audfprint_store: HashTable.store (afp/audfprint/hash_table.py:72-113) for a batch of entries.  rows (N,2) int32
+ * (time, hash) and ids (N) int32 in arrival order; order (N) int64 = the arrival indices stably sorted by hash & mask;
+ * seg_start (n_seg + 1) int32 = offsets into `order` of each bucket's run.  Slots are arrival ranks; a full bucket draws
+ * slot uniform over 0..count from a counter-based generator keyed by (seed, bucket, count) -- the reference draws from
+ * Python's global `random` (:99-103) -- and stores only when slot < depth; counts keep growing.  (id + 1) << timebits
+ * must fit 32 bits (the caller checks).
+ *
+ * mfpa_audfprint_match: Matcher.match_hashes without exact_count / find_time_range (afp/audfprint/audfprint_match.py:322-346:
+ * get_hits, _best_count_ids :105-137, _approx_match_counts :236-320, the sort by filtered count) for B queries.
+ *   hashes (B,cap,2) int32 (time, hash), nq (B) int32 rows per query (the layout of mfpa_audfprint_landmarks' uniq);
+ *   scratch: B * mfpa_audfprint_match_scratch_bytes(hcap) bytes, hcap a power of two in [64, 2^26] (hits per query);
+ *   out (B,K,7) int32 rows [id, filtered_count, time_offset, raw_count, orig_rank, 0, 0], filtered count descending,
+ *   ties by (orig_rank, mode order); rows past info[1] are not written;
+ *   info (B,3) int32 = [n_hits, rows written, rows in total], or [n_hits, -1, -1] when n_hits > hcap (nothing else is
+ *   written: call again with a larger hcap).  search_depth <= 256; ties in the weighted count rank the larger id first.
+ */
+int mfpa_audfprint_store(const int32_t* rows, const int32_t* ids, const int64_t* order, const int32_t* seg_start, int n_seg,
+                         int hashbits, int timebits, int depth, unsigned long long seed, uint32_t* table, int32_t* counts,
+                         void* stream);
+int mfpa_audfprint_match_scratch_bytes(long long hcap, long long* bytes);
+int mfpa_audfprint_match(const uint32_t* table, const int32_t* counts, const int32_t* hashesperid, int n_ids, int hashbits,
+                         int timebits, int depth, const int32_t* hashes, const int32_t* nq, int B, int cap, int threshcount,
+                         int search_depth, int window, int max_alignments, long long hcap, void* scratch, int K, int32_t* out,
+                         int32_t* info, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * UNet denoiser building blocks, training/unet.py:8-108.  Activations are NHWC float32
  * ("pixels x channels": H = frequency bins, W = frames); with C = 1 at both ends of the
  * network this is byte-identical to the reference's NCHW (B,1,257,T) tensors.

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_double, c_float, c_int, c_longlong, c_uint, c_void_p
+from ctypes import c_double, c_float, c_int, c_longlong, c_uint, c_ulonglong, c_void_p
 
 import torch  # noqa: F401  (must precede the dlopen below)
 
@@ -20,7 +20,7 @@ EINVAL = -22
 EHIP = -1000
 F32, F64 = 0, 1
 STFT_TABLE_LEN = 1288
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 
 class MfpaError(RuntimeError):
@@ -56,6 +56,11 @@ _SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_dejavu_hashes": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                             c_void_p, c_void_p], c_int),
+    "mfpa_audfprint_store": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ulonglong, c_void_p,
+                              c_void_p, c_void_p], c_int),
+    "mfpa_audfprint_match_scratch_bytes": ([c_longlong, c_void_p], c_int),
+    "mfpa_audfprint_match": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                              c_int, c_int, c_int, c_int, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_conv3x3_bn_relu": ([c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                               c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p], c_int),
     "mfpa_conv3x3_c1_bn_relu": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,

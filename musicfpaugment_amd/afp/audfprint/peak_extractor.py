@@ -148,11 +148,18 @@ class Audfprint_peaks(object):
         d = self._read_waveform(filename, self.target_sr).reshape(1, -1).to(self.device)
         if self.demucs is not None:
             d = self.demucs(d)[:, 0].contiguous()
+        self.soundfiledur = d.shape[1] / self.target_sr
         uq, n = self.hashes_batch(d)
         n0 = int(n[0])
         if n0 < 0:                                           # never a slice bound: hashes_batch raises on overflow, this guards the contract
             raise ValueError("landmark capacity exceeded")
         return uq[0, :n0].cpu().numpy().astype(np.int32)
+
+    def ingest(self, hashtable, filename: str) -> Tuple[float, int]:
+        """peak_extractor.py:462-481: add one file's hashes to `hashtable` (hash_table.HashTable); (duration, n hashes)."""
+        hashes = self.wavfile2hashes(filename)
+        hashtable.store(filename, hashes)
+        return self.soundfiledur, len(hashes)
 
     # ------------------------------------------------------------------ landmarks / hashes (next-tier row §8f-1)
     def hashes_batch(self, wav: torch.Tensor, cap: int = 4096, shifts: Optional[int] = None):

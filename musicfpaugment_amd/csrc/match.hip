@@ -1,0 +1,454 @@
+// Audfprint hash table and matcher for MI355X (gfx950): HashTable.store / get_hits and
+// Matcher._best_count_ids / _approx_match_counts / the final sort of match_hashes
+// (afp/audfprint/hash_table.py:72-113, :222-247; afp/audfprint/audfprint_match.py:105-137, :236-320, :322-346).
+// Integer arithmetic throughout except the weighted count rawcount / hashesperid, one float64 division as in numpy.
+//
+// store: one thread per (bucket) segment of a batch of entries already grouped by bucket in arrival order (a stable sort
+//   done by the caller).  The thread walks its segment in arrival order, so in-bucket slots are arrival ranks exactly as
+//   the reference assigns them; a full bucket takes the reservoir step (slot uniform over 0..count, stored only when
+//   slot < depth) with the slot drawn from a counter-based generator keyed by (seed, bucket, arrival index in the bucket)
+//   instead of Python's global `random` -- DESIGN.md §3.8.
+//
+// match: one workgroup per query, all of it in the query's slice of a global scratch buffer:
+//   1. gather  every table entry of every query hash -> 64-bit key (id << 32 | biased dt); the count is reported, and a
+//              query whose hits exceed the scratch capacity writes nothing else (the caller retries with a larger one);
+//   2. sort    bitonic: LDS chunks of 4096 keys, global passes only for strides >= one chunk;
+//   3. runs    run lengths of equal keys = the sparse dt histogram of each id (rcnt), run lengths of equal ids = rawcounts;
+//   4. rank    ids ordered by rawcount / hashesperid (float64) descending, ties larger id first (numpy's argsort(...)[::-1]
+//              on a stable order); the first min(#(rawcount > threshcount), search_depth) are the candidates;
+//   5. modes   one wave per candidate: locmax on the sparse histogram (implicit zeros between runs), repeated first-index
+//              argmax, windowed sum of the unfiltered counts, zeroing of the window, at most max_alignments + 1 modes;
+//   6. order   rows by filtered count descending, ties by (candidate rank, mode order); the first K are written.
+#include "mfpa_common.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kChunk = 4096;          // uint64 keys per LDS sort chunk (32 KiB)
+constexpr int kMaxCand = 256;         // search_depth limit (LDS candidate arrays)
+
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+__global__ __launch_bounds__(kBlock) void store_kernel(const int32_t* __restrict__ rows, const int32_t* __restrict__ ids,
+                                                        const int64_t* __restrict__ order, const int32_t* __restrict__ seg,
+                                                        int n_seg, uint32_t hmask, int timebits, int depth,
+                                                        unsigned long long seed, uint32_t* __restrict__ table,
+                                                        int32_t* __restrict__ counts) {
+  const int s = blockIdx.x * kBlock + threadIdx.x;
+  if (s >= n_seg) return;
+  const int lo = seg[s], hi = seg[s + 1];
+  if (lo >= hi) return;
+  const uint32_t bucket = (uint32_t)rows[2 * order[lo] + 1] & hmask;
+  const uint32_t tmask = (1u << timebits) - 1u;
+  uint32_t* row = table + (size_t)bucket * depth;
+  int c = counts[bucket];
+  for (int j = lo; j < hi; ++j, ++c) {
+    const long long i = order[j];
+    const uint32_t val = ((uint32_t)(ids[i] + 1) << timebits) | ((uint32_t)rows[2 * i] & tmask);
+    if (c < depth) {
+      row[c] = val;
+    } else {
+      // hash_table.py:99-103: slot = random.randint(0, count); stored only if slot < depth
+      const unsigned long long r = splitmix64(seed ^ splitmix64(((unsigned long long)bucket << 32) | (uint32_t)c));
+      const unsigned long long slot = __umul64hi(r, (unsigned long long)c + 1ull);
+      if (slot < (unsigned long long)depth) row[slot] = val;
+    }
+  }
+  counts[bucket] = c;
+}
+
+// Block-wide exclusive scan of one int per thread; *total gets the sum.  All threads must call it.
+__device__ __forceinline__ int block_excl_scan(int v, int* sh, int* total) {
+  const int tid = threadIdx.x;
+  sh[tid] = v;
+  __syncthreads();
+  for (int off = 1; off < kBlock; off <<= 1) {
+    const int x = tid >= off ? sh[tid - off] : 0;
+    __syncthreads();
+    sh[tid] += x;
+    __syncthreads();
+  }
+  const int incl = sh[tid];
+  *total = sh[kBlock - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+// Bitonic compare-exchange passes j = jstart .. 1 of stage k on s[0, len), global index of s[0] = gbase.
+__device__ __forceinline__ void lds_bitonic(unsigned long long* s, int len, long long gbase, long long k, int jstart) {
+  for (int j = jstart; j > 0; j >>= 1) {
+    for (int i = threadIdx.x; i < len; i += kBlock) {
+      const int l = i ^ j;
+      if (l > i) {
+        const bool asc = ((gbase + i) & k) == 0;
+        const unsigned long long a = s[i], b = s[l];
+        if ((a > b) == asc) {
+          s[i] = b;
+          s[l] = a;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ void sort_keys(unsigned long long* keys, long long P, unsigned long long* sk) {
+  const int tid = threadIdx.x;
+  if (P <= kChunk) {
+    for (int i = tid; i < P; i += kBlock) sk[i] = keys[i];
+    __syncthreads();
+    for (long long k = 2; k <= P; k <<= 1) lds_bitonic(sk, (int)P, 0, k, (int)(k >> 1));
+    for (int i = tid; i < P; i += kBlock) keys[i] = sk[i];
+    __syncthreads();
+    return;
+  }
+  for (long long c = 0; c < P; c += kChunk) {
+    for (int i = tid; i < kChunk; i += kBlock) sk[i] = keys[c + i];
+    __syncthreads();
+    for (long long k = 2; k <= kChunk; k <<= 1) lds_bitonic(sk, kChunk, c, k, (int)(k >> 1));
+    for (int i = tid; i < kChunk; i += kBlock) keys[c + i] = sk[i];
+    __syncthreads();
+  }
+  for (long long k = 2 * kChunk; k <= P; k <<= 1) {
+    for (long long j = k >> 1; j >= kChunk; j >>= 1) {
+      for (long long i = tid; i < P; i += kBlock) {
+        const long long l = i ^ j;
+        if (l > i) {
+          const bool asc = (i & k) == 0;
+          const unsigned long long a = keys[i], b = keys[l];
+          if ((a > b) == asc) {
+            keys[i] = b;
+            keys[l] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+    for (long long c = 0; c < P; c += kChunk) {
+      for (int i = tid; i < kChunk; i += kBlock) sk[i] = keys[c + i];
+      __syncthreads();
+      lds_bitonic(sk, kChunk, c, k, kChunk >> 1);
+      for (int i = tid; i < kChunk; i += kBlock) keys[c + i] = sk[i];
+      __syncthreads();
+    }
+  }
+}
+
+__device__ __forceinline__ int key_id(unsigned long long k) { return (int)(uint32_t)(k >> 32); }
+__device__ __forceinline__ int key_dt(unsigned long long k) { return (int)((uint32_t)k ^ 0x80000000u); }
+
+struct MatchArgs {
+  const uint32_t* table;
+  const int32_t* counts;
+  const int32_t* hashesperid;
+  int n_ids, timebits, depth;
+  uint32_t hmask;
+  const int32_t* hashes;
+  const int32_t* nq;
+  int cap, thresh, search_depth, window, max_modes;
+  long long hcap;
+  unsigned char* scratch;
+  int K;
+  int32_t* out;
+  int32_t* info;
+};
+
+__global__ __launch_bounds__(kBlock) void match_kernel(MatchArgs a) {
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long hcap = a.hcap;
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(a.scratch + (size_t)b * (size_t)hcap * 32);
+  unsigned long long* rkey = keys + hcap;                 // run keys
+  int32_t* rcnt = reinterpret_cast<int32_t*>(rkey + hcap); // run lengths = unfiltered histogram values
+  int32_t* rfilt = rcnt + hcap;                            // run start (phase 3), then the filtered histogram
+  int32_t* idrun = rfilt + hcap;                           // first run of each distinct id
+  int32_t* idraw = idrun + hcap;                           // rawcount of each distinct id
+  double* wts = reinterpret_cast<double*>(keys);           // phase 4 (keys are dead after phase 3)
+  int32_t* rows = reinterpret_cast<int32_t*>(keys);        // phase 5-6: (count, dt) pairs at the candidate's run indices
+
+  __shared__ unsigned long long sk[kChunk];
+  __shared__ int sh[kBlock];
+  __shared__ double rw[kBlock];
+  __shared__ int rid[kBlock], rm[kBlock];
+  __shared__ int c_m[kMaxCand], c_nrow[kMaxCand], c_off[kMaxCand + 1];
+  __shared__ long long s_n;
+
+  // ---- 1. gather (hash_table.py:222-247): query hashes masked to hashbits, query times not masked
+  const int n = min(max(a.nq[b], 0), a.cap);
+  const int32_t* Q = a.hashes + (size_t)b * a.cap * 2;
+  if (tid == 0) s_n = 0;
+  __syncthreads();
+  const uint32_t tmask = (1u << a.timebits) - 1u;
+  for (int i = tid; i < n; i += kBlock) {
+    const int t = Q[2 * i];
+    const uint32_t h = (uint32_t)Q[2 * i + 1] & a.hmask;
+    const int nb = min(max(a.counts[h], 0), a.depth);
+    if (nb == 0) continue;
+    const long long pos = (long long)atomicAdd(reinterpret_cast<unsigned long long*>(&s_n), (unsigned long long)nb);
+    const uint32_t* tv = a.table + (size_t)h * a.depth;
+    for (int s = 0; s < nb && pos + s < hcap; ++s) {
+      const uint32_t v = tv[s];
+      const int id = (int)(v >> a.timebits) - 1;
+      const int dt = (int)(v & tmask) - t;
+      keys[pos + s] = ((unsigned long long)(uint32_t)id << 32) | ((uint32_t)dt ^ 0x80000000u);
+    }
+  }
+  __syncthreads();
+  const long long nh = s_n;
+  int32_t* info = a.info + (size_t)b * 3;
+  if (nh > hcap) {                                         // reported, never truncated: the caller retries with a larger hcap
+    if (tid == 0) {
+      info[0] = (int32_t)min(nh, (long long)INT32_MAX);
+      info[1] = -1;
+      info[2] = -1;
+    }
+    return;
+  }
+
+  // ---- 2. sort (id, dt) keys
+  if (nh > 1) {
+    long long P = 1;
+    while (P < nh) P <<= 1;
+    for (long long i = nh + tid; i < P; i += kBlock) keys[i] = ~0ull;
+    __syncthreads();
+    sort_keys(keys, P, sk);
+  }
+  const int NH = (int)nh;
+
+  // ---- 3. runs: sparse per-id dt histograms (np.bincount, audfprint_match.py:275) and rawcounts (:117)
+  int R = 0;
+  for (int base = 0; base < NH; base += kBlock) {
+    const int i = base + tid;
+    const int flag = i < NH && (i == 0 || keys[i] != keys[i - 1]);
+    int tot;
+    const int ex = block_excl_scan(flag, sh, &tot);
+    if (flag) {
+      rkey[R + ex] = keys[i];
+      rfilt[R + ex] = i;
+    }
+    R += tot;
+  }
+  __syncthreads();
+  for (int r = tid; r < R; r += kBlock) rcnt[r] = (r + 1 < R ? rfilt[r + 1] : NH) - rfilt[r];
+  int M = 0;
+  for (int base = 0; base < R; base += kBlock) {
+    const int r = base + tid;
+    const int flag = r < R && (r == 0 || key_id(rkey[r]) != key_id(rkey[r - 1]));
+    int tot;
+    const int ex = block_excl_scan(flag, sh, &tot);   // its barriers also order the rcnt writes above
+    if (flag) idrun[M + ex] = r;
+    M += tot;
+  }
+  __syncthreads();
+  for (int m = tid; m < M; m += kBlock) {
+    const int e = m + 1 < M ? idrun[m + 1] : R;
+    idraw[m] = (e < R ? rfilt[e] : NH) - rfilt[idrun[m]];
+  }
+  __syncthreads();
+  // locmax (audfprint_match.py:24-40): >= the left neighbour, > the right one; zeros between runs are implicit
+  for (int r = tid; r < R; r += kBlock) {
+    const int id = key_id(rkey[r]), dt = key_dt(rkey[r]), c = rcnt[r];
+    const int left = (r > 0 && key_id(rkey[r - 1]) == id && key_dt(rkey[r - 1]) == dt - 1) ? rcnt[r - 1] : 0;
+    const int right = (r + 1 < R && key_id(rkey[r + 1]) == id && key_dt(rkey[r + 1]) == dt + 1) ? rcnt[r + 1] : 0;
+    rfilt[r] = (c >= left && c > right) ? c : 0;
+  }
+
+  // ---- 4. candidates (_best_count_ids, audfprint_match.py:105-137)
+  int above = 0;
+  for (int m = tid; m < M; m += kBlock) {
+    const int id = key_id(rkey[idrun[m]]);
+    const bool ok = id >= 0 && id < a.n_ids;
+    wts[m] = ok ? (double)idraw[m] / (double)a.hashesperid[id] : -1.0;
+    above += ok && idraw[m] > a.thresh;
+  }
+  int n_above;
+  block_excl_scan(above, sh, &n_above);
+  const int D = min(n_above, a.search_depth);
+  double pw = INFINITY;
+  int pid = INT32_MAX;                                     // previous pick: (weight, id); the next one comes strictly after it
+  for (int c = 0; c < D; ++c) {
+    double bw = -1.0;
+    int bid = -1, bm = -1;
+    for (int m = tid; m < M; m += kBlock) {
+      const double w = wts[m];
+      if (w < 0) continue;
+      const int id = key_id(rkey[idrun[m]]);
+      const bool after_prev = w < pw || (w == pw && id < pid);
+      const bool better = w > bw || (w == bw && id > bid);
+      if (after_prev && better) {
+        bw = w;
+        bid = id;
+        bm = m;
+      }
+    }
+    rw[tid] = bw;
+    rid[tid] = bid;
+    rm[tid] = bm;
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+      if (tid < o) {
+        const double w2 = rw[tid + o];
+        const int id2 = rid[tid + o];
+        if (w2 > rw[tid] || (w2 == rw[tid] && id2 > rid[tid])) {
+          rw[tid] = w2;
+          rid[tid] = id2;
+          rm[tid] = rm[tid + o];
+        }
+      }
+      __syncthreads();
+    }
+    pw = rw[0];
+    pid = rid[0];
+    if (tid == 0) c_m[c] = rm[0];
+    __syncthreads();
+  }
+
+  // ---- 5. modes (_approx_match_counts, audfprint_match.py:281-318), one wave per candidate
+  for (int c = wave; c < D; c += kBlock / 64) {
+    const int m = c_m[c];
+    const int s = idrun[m], e = m + 1 < M ? idrun[m + 1] : R;
+    int nrow = 0;
+    for (int found = 0; found < a.max_modes; ++found) {
+      int v = 0, idx = -1;
+      for (int r = s + lane; r < e; r += 64) {
+        const int f = rfilt[r];
+        if (f > v) {
+          v = f;
+          idx = r;
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const int v2 = __shfl_xor(v, o), i2 = __shfl_xor(idx, o);
+        if (v2 > v || (v2 == v && i2 >= 0 && (idx < 0 || i2 < idx))) {
+          v = v2;
+          idx = i2;
+        }
+      }
+      if (v <= a.thresh) break;                            // first-index argmax of the filtered histogram <= threshcount
+      const int dtm = key_dt(rkey[idx]);
+      int count = 0;
+      for (int r = idx; r >= s && key_dt(rkey[r]) >= dtm - a.window; --r) {
+        count += rcnt[r];
+        if (((r - s) & 63) == lane) rfilt[r] = 0;          // each lane clears only the runs it scans above
+      }
+      for (int r = idx + 1; r < e && key_dt(rkey[r]) <= dtm + a.window; ++r) {
+        count += rcnt[r];
+        if (((r - s) & 63) == lane) rfilt[r] = 0;
+      }
+      if (lane == 0) {
+        rows[2 * (s + nrow)] = count;
+        rows[2 * (s + nrow) + 1] = dtm;
+      }
+      ++nrow;
+    }
+    if (lane == 0) c_nrow[c] = nrow;
+  }
+  __syncthreads();
+
+  // ---- 6. final order (match_hashes, audfprint_match.py:336): filtered count descending, ties (rank, mode order)
+  if (tid == 0) {
+    int o = 0;
+    for (int c = 0; c < D; ++c) {
+      c_off[c] = o;
+      o += c_nrow[c];
+    }
+    c_off[D] = o;
+  }
+  __syncthreads();
+  const int Rt = c_off[D];
+  int32_t* out = a.out + (size_t)b * a.K * 7;
+  for (int f = tid; f < Rt; f += kBlock) {
+    int c = 0;
+    while (c_off[c + 1] <= f) ++c;
+    const int m = c_m[c], s = idrun[m], k = f - c_off[c];
+    const int cnt = rows[2 * (s + k)];
+    int pos = 0;
+    for (int c2 = 0; c2 < D; ++c2) {
+      const int s2 = idrun[c_m[c2]];
+      for (int k2 = 0; k2 < c_nrow[c2]; ++k2) {
+        const int cg = rows[2 * (s2 + k2)];
+        pos += cg > cnt || (cg == cnt && c_off[c2] + k2 < f);
+      }
+    }
+    if (pos < a.K) {
+      int32_t* o = out + (size_t)pos * 7;
+      o[0] = key_id(rkey[s]);
+      o[1] = cnt;
+      o[2] = rows[2 * (s + k) + 1];
+      o[3] = idraw[m];
+      o[4] = c;
+      o[5] = 0;
+      o[6] = 0;
+    }
+  }
+  if (tid == 0) {
+    info[0] = NH;
+    info[1] = min(Rt, a.K);
+    info[2] = Rt;
+  }
+}
+
+bool valid_table(int hashbits, int timebits, int depth) {
+  return hashbits >= 1 && hashbits <= 24 && timebits >= 1 && timebits <= 20 && depth >= 1 && depth <= 4096;
+}
+
+}  // namespace
+
+extern "C" int mfpa_audfprint_store(const int32_t* rows, const int32_t* ids, const int64_t* order, const int32_t* seg_start,
+                                    int n_seg, int hashbits, int timebits, int depth, unsigned long long seed,
+                                    uint32_t* table, int32_t* counts, void* stream) {
+  if (n_seg < 0 || !valid_table(hashbits, timebits, depth)) return MFPA_EINVAL;
+  if (n_seg == 0) return MFPA_OK;
+  if (!rows || !ids || !order || !seg_start || !table || !counts) return MFPA_EINVAL;
+  hipLaunchKernelGGL(store_kernel, dim3((n_seg + kBlock - 1) / kBlock), dim3(kBlock), 0, mfpa_stream(stream), rows, ids,
+                     order, seg_start, n_seg, (uint32_t)((1ull << hashbits) - 1), timebits, depth, seed, table, counts);
+  MFPA_CHECK_LAUNCH();
+  return MFPA_OK;
+}
+
+extern "C" int mfpa_audfprint_match_scratch_bytes(long long hcap, long long* bytes) {
+  if (!bytes || hcap < 64 || hcap > (1ll << 26) || (hcap & (hcap - 1))) return MFPA_EINVAL;
+  *bytes = hcap * 32;
+  return MFPA_OK;
+}
+
+extern "C" int mfpa_audfprint_match(const uint32_t* table, const int32_t* counts, const int32_t* hashesperid, int n_ids,
+                                    int hashbits, int timebits, int depth, const int32_t* hashes, const int32_t* nq, int B,
+                                    int cap, int threshcount, int search_depth, int window, int max_alignments,
+                                    long long hcap, void* scratch, int K, int32_t* out, int32_t* info, void* stream) {
+  if (B < 0 || cap < 0 || n_ids < 0 || !valid_table(hashbits, timebits, depth)) return MFPA_EINVAL;
+  if (threshcount < 0 || search_depth < 0 || search_depth > kMaxCand || window < 0 || window > 1024 || max_alignments < 0 ||
+      max_alignments >= INT32_MAX || K < 1)
+    return MFPA_EINVAL;
+  if (hcap < 64 || hcap > (1ll << 26) || (hcap & (hcap - 1))) return MFPA_EINVAL;   // a power of two: the bitonic sort pads to one
+  if (B == 0) return MFPA_OK;
+  if (!table || !counts || !hashesperid || !hashes || !nq || !scratch || !out || !info) return MFPA_EINVAL;
+  MatchArgs a;
+  a.table = table;
+  a.counts = counts;
+  a.hashesperid = hashesperid;
+  a.n_ids = n_ids;
+  a.timebits = timebits;
+  a.depth = depth;
+  a.hmask = (uint32_t)((1ull << hashbits) - 1);
+  a.hashes = hashes;
+  a.nq = nq;
+  a.cap = cap;
+  a.thresh = threshcount;
+  a.search_depth = search_depth;
+  a.window = window;
+  a.max_modes = max_alignments + 1;
+  a.hcap = hcap;
+  a.scratch = static_cast<unsigned char*>(scratch);
+  a.K = K;
+  a.out = out;
+  a.info = info;
+  hipLaunchKernelGGL(match_kernel, dim3(B), dim3(kBlock), 0, mfpa_stream(stream), a);
+  MFPA_CHECK_LAUNCH();
+  return MFPA_OK;
+}

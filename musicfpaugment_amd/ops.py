@@ -358,3 +358,81 @@ def psnr_stats(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     out = torch.empty((B, 3), dtype=torch.float64, device=pred.device)
     check(lib().mfpa_psnr_stats(ptr(pred), _dtype_code(pred), ptr(target), B, n, ptr(out), stream()), "mfpa_psnr_stats")
     return out
+
+
+# ----------------------------------------------------------------------------- Audfprint hash table / matcher
+def audfprint_store(table: torch.Tensor, counts: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, seed: int = 0,
+                    timebits: int = 14) -> None:
+    """HashTable.store (hash_table.py:72-113) of N entries in arrival order, in place: table (2^hashbits, depth) int32
+    (bit pattern of the reference's uint32), counts (2^hashbits,) int32, rows (N, 2) int32 (time, hash), ids (N,) int32.
+    Torch only groups the entries by bucket (a stable sort); the slot assignment and the reservoir step run in the kernel."""
+    for t, name in ((table, "table"), (counts, "counts"), (rows, "rows"), (ids, "ids")):
+        require_gpu(t, name)
+        if t.dtype != torch.int32:
+            raise TypeError(f"{name} must be int32")
+    nb, depth = table.shape
+    hashbits = nb.bit_length() - 1
+    if nb != 1 << hashbits or counts.shape != (nb,):
+        raise ValueError("table must have 2^hashbits rows and counts one entry per row")
+    N = rows.shape[0]
+    if rows.shape != (N, 2) or ids.shape != (N,):
+        raise ValueError("rows must be (N, 2) and ids (N,)")
+    if N == 0:
+        return
+    bucket = rows[:, 1].to(torch.int64) & (nb - 1)
+    sb, order = torch.sort(bucket, stable=True)
+    _, seg_counts = torch.unique_consecutive(sb, return_counts=True)
+    seg = torch.zeros(seg_counts.numel() + 1, dtype=torch.int32, device=rows.device)
+    seg[1:] = torch.cumsum(seg_counts, 0)
+    check(lib().mfpa_audfprint_store(ptr(rows.contiguous()), ptr(ids.contiguous()), ptr(order.contiguous()), ptr(seg),
+                                     int(seg_counts.numel()), hashbits, timebits, depth, int(seed) & ((1 << 64) - 1),
+                                     ptr(table), ptr(counts), stream()), "mfpa_audfprint_store")
+
+
+def match_scratch_bytes(hcap: int) -> int:
+    n = ctypes.c_longlong(0)
+    check(lib().mfpa_audfprint_match_scratch_bytes(int(hcap), ctypes.addressof(n)), "mfpa_audfprint_match_scratch_bytes")
+    return int(n.value)
+
+
+def audfprint_match(table: torch.Tensor, counts: torch.Tensor, hashesperid: torch.Tensor, hashes: torch.Tensor,
+                    nq: torch.Tensor, k: int = 1, threshcount: int = 5, search_depth: int = 100, window: int = 2,
+                    max_alignments_per_id: int = 100, hcap: int = 1 << 15, timebits: int = 14,
+                    scratch_budget: int = 1 << 30) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """Matcher.match_hashes (audfprint_match.py:322-346, approximate counts) for B queries: hashes (B, cap, 2) int32
+    (time, hash) with nq (B,) valid rows each -> (rows (B, k, 7) int32 sorted by filtered count, info (B, 3) int32
+    [n_hits, rows written, rows in total], the hit capacity used).  A query with more hits than the scratch capacity is
+    reported by the kernel and the batch runs again with a capacity that holds it: nothing is truncated."""
+    for t, name in ((table, "table"), (counts, "counts"), (hashesperid, "hashesperid"), (hashes, "hashes"), (nq, "nq")):
+        require_gpu(t, name)
+        if t.dtype != torch.int32:
+            raise TypeError(f"{name} must be int32")
+    nb, depth = table.shape
+    hashbits = nb.bit_length() - 1
+    if hashes.dim() != 3 or hashes.shape[2] != 2 or nq.shape != (hashes.shape[0],):
+        raise ValueError("hashes must be (B, cap, 2) and nq (B,)")
+    B, cap = hashes.shape[0], hashes.shape[1]
+    dev = hashes.device
+    out = torch.zeros((B, k, 7), dtype=torch.int32, device=dev)
+    info = torch.zeros((B, 3), dtype=torch.int32, device=dev)
+    if B == 0:
+        return out, info, hcap
+    hashes, nq = hashes.contiguous(), nq.contiguous()
+    while True:
+        per_q = match_scratch_bytes(hcap)
+        chunk = max(1, min(B, scratch_budget // per_q))
+        scratch = torch.empty(chunk * per_q, dtype=torch.uint8, device=dev)
+        for s in range(0, B, chunk):
+            e = min(B, s + chunk)
+            check(lib().mfpa_audfprint_match(ptr(table), ptr(counts), ptr(hashesperid), hashesperid.numel(), hashbits, timebits,
+                                             depth, ptr(hashes[s:e]), ptr(nq[s:e]), e - s, cap, threshcount, search_depth,
+                                             window, max_alignments_per_id, hcap, ptr(scratch), k, ptr(out[s:e]),
+                                             ptr(info[s:e]), stream()), "mfpa_audfprint_match")
+        del scratch
+        need = int(info[:, 0].max())
+        if need <= hcap:
+            return out, info, hcap
+        if need > 1 << 26:
+            raise ValueError(f"a query has {need} table hits: more than the matcher's limit of 2^26 per query")
+        while hcap < need:
+            hcap <<= 1

@@ -89,3 +89,160 @@ def compute_peaks_metrics_files(queries_augmented, clean_dir: str, analyzer_no_d
     if len({len(a) for a in aug} | {len(c) for c in clean}) > 1:
         raise ValueError("queries of different lengths: group them by length before calling the batched harness")
     return compute_peaks_metrics(torch.stack(clean), torch.stack(aug), analyzer_no_den, analyzer_den, batch=batch)
+
+
+# ----------------------------------------------------------------------------- identification rate (audfprint_exps.py:17-84)
+MAX_TRACK_FRAMES = 1500          # the pruner's frame limit (ops.audfprint_prune): 1 + n_samples // 256 <= 1500, ~48 s at 8 kHz
+
+
+def _check_track_length(n_samples: int, what: str) -> None:
+    frames = 1 + n_samples // 256
+    if frames > MAX_TRACK_FRAMES:
+        raise ValueError(f"{what}: {n_samples} samples = {frames} STFT frames; the device peak picker takes at most "
+                         f"{MAX_TRACK_FRAMES} frames ({MAX_TRACK_FRAMES * 256 / 8000:.0f} s at 8 kHz) per clip, and the landmark "
+                         "kernel at most 8192 landmarks: split longer tracks")
+
+
+def _database_analyzer(device):
+    from ..constants import afp_settings
+    a = Audfprint_peaks(afp_settings["audfprint"], device=device)
+    a.shifts = 1                                                     # audfprint_exps.py:20-21
+    return a
+
+
+@torch.no_grad()
+def create_fp_database_batch(tracks, names, ht=None, analyzer: Audfprint_peaks = None, batch: int = 64, device=None):
+    """Fingerprint database of `tracks` (a (N, T) tensor or a sequence of 1-D waveforms of any lengths up to the limit
+    above), stored under `names` in the given order.  Tracks are fingerprinted in batches of equal length on the device
+    (hashes_batch with shifts = 1, as create_fp_database) and stored in file order with HashTable.store_batch.  Returns the
+    HashTable."""
+    from ..afp.audfprint.hash_table import HashTable
+    device = torch.device(device if device is not None else (analyzer.device if analyzer is not None else "cuda"))
+    analyzer = analyzer or _database_analyzer(device)
+    ht = ht if ht is not None else HashTable(device=device)
+    tracks = list(tracks)
+    if len(tracks) != len(names):
+        raise ValueError("one name per track")
+    for i, t in enumerate(tracks):
+        _check_track_length(int(torch.as_tensor(t).shape[-1]), f"track {i} ({names[i]})")
+    by_len = {}
+    for i, t in enumerate(tracks):
+        by_len.setdefault(int(torch.as_tensor(t).shape[-1]), []).append(i)
+    per_track = [None] * len(tracks)
+    for _, idx in sorted(by_len.items()):
+        for s in range(0, len(idx), batch):
+            chunk = idx[s:s + batch]
+            wav = torch.stack([torch.as_tensor(tracks[i], dtype=torch.float32).reshape(-1) for i in chunk]).to(device)
+            uq, n = analyzer.hashes_batch(wav.contiguous(), shifts=1)
+            for j, i in enumerate(chunk):
+                per_track[i] = (uq[j], n[j])
+    cap = max([u.shape[0] for u, _ in per_track], default=1)
+    for s in range(0, len(tracks), batch):                           # file order
+        part = per_track[s:s + batch]
+        uq = torch.zeros((len(part), cap, 2), dtype=torch.int32, device=device)
+        for j, (u, _) in enumerate(part):
+            uq[j, : u.shape[0]] = u
+        ht.store_batch(names[s:s + batch], uq, torch.stack([n for _, n in part]))
+    return ht
+
+
+def _query_hashes(analyzer: Audfprint_peaks, wav: torch.Tensor):
+    if analyzer.demucs is not None:                                  # wavfile2peaks: Demucs acts on the waveform (:369-376)
+        wav = analyzer.demucs(wav)[:, 0].contiguous()
+    return analyzer.hashes_batch(wav)
+
+
+@torch.no_grad()
+def compute_accuracy_batch(queries: torch.Tensor, gt_ids, ht, analyzer1: Audfprint_peaks, analyzer2: Audfprint_peaks,
+                           batch: int = 256, per_query: bool = False, matcher=None):
+    """compute_accuracy (audfprint_exps.py:24-84) for query waveforms already in memory: queries (N, T) float32, gt_ids (N,)
+    the database id of each query's track.  Each query is fingerprinted by both analyzers (their `shifts`, 4 in the
+    experiment) and matched on the device (Matcher.match_batch, top row).  Returns the reference's dictionary; with
+    per_query=True also the (N, 4) int64 tensor [id1, count1, id2, count2] behind it (id -1: NOMATCH, count 0).  With
+    torch.distributed initialised the queries are split over ranks and the rows gathered: identical to one GPU, because
+    every rank builds the same table (the store is deterministic)."""
+    import torch.distributed as dist
+    from ..afp.audfprint.audfprint_match import Matcher
+    matcher = matcher or Matcher()
+    N = queries.shape[0]
+    _check_track_length(int(queries.shape[1]), "queries")
+    gt = torch.as_tensor(gt_ids, dtype=torch.int64).reshape(-1)
+    if gt.numel() != N:
+        raise ValueError("one ground-truth id per query")
+    ddp = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    rank, world = (dist.get_rank(), dist.get_world_size()) if ddp else (0, 1)
+    lo, hi = shard_range(N, rank, world)
+    dev = ht.table.device
+    rows = []
+    for s in range(lo, hi, batch):
+        e = min(hi, s + batch)
+        wav = queries[s:e].to(dev, torch.float32).contiguous()
+        cols = []
+        for an in (analyzer1, analyzer2):
+            uq, n = _query_hashes(an, wav)
+            top, info = matcher.match_batch(ht, uq, n, k=1)
+            hit = info[:, 1] > 0
+            cols.append(torch.where(hit, top[:, 0, 0], -1).to(torch.int64))
+            cols.append(torch.where(hit, top[:, 0, 1], 0).to(torch.int64))
+        rows.append(torch.stack(cols, dim=1))
+    local = torch.cat(rows) if rows else torch.zeros((0, 4), dtype=torch.int64, device=dev)
+    if ddp:
+        sizes = [shard_range(N, r, world)[1] - shard_range(N, r, world)[0] for r in range(world)]
+        pad = torch.zeros((max(sizes), 4), dtype=torch.int64, device=dev)
+        pad[: local.shape[0]] = local
+        gathered = [torch.empty_like(pad) for _ in range(world)]
+        dist.all_gather(gathered, pad)
+        local = torch.cat([g[:n] for g, n in zip(gathered, sizes)])
+    res = accuracy_from_rows(local.cpu(), gt)
+    return (res, local) if per_query else res
+
+
+def accuracy_from_rows(rows: torch.Tensor, gt: torch.Tensor):
+    """[id1, count1, id2, count2] per query -> the reference's accuracies; "mix" takes analyzer 1's answer when its filtered
+    count is >= analyzer 2's (audfprint_exps.py:58-73)."""
+    rows = rows.to(torch.int64)
+    gt = torch.as_tensor(gt, dtype=torch.int64).reshape(-1)
+    N = max(rows.shape[0], 1)
+    ok1 = (rows[:, 0] >= 0) & (rows[:, 0] == gt)
+    ok2 = (rows[:, 2] >= 0) & (rows[:, 2] == gt)
+    mix = torch.where(rows[:, 1] >= rows[:, 3], ok1, ok2)
+    return {"No Denoising": int(ok1.sum()) / N, "With Denoising": int(ok2.sum()) / N, "Mix Pipeline": int(mix.sum()) / N}
+
+
+def create_fp_database(files, dbpath: str, device=None) -> None:
+    """audfprint_exps.py:17-27: ingest every file (unreadable ones are reported and skipped), save to dbpath."""
+    from ..afp.audfprint.hash_table import HashTable
+    hash_tab = HashTable(device=device)
+    analyzer = _database_analyzer(hash_tab.device)
+    for filename in files:
+        try:
+            analyzer.ingest(hash_tab, filename)
+        except Exception:
+            print("error with ", filename)
+    hash_tab.save(dbpath)
+
+
+def compute_accuracy(files, dbpath: str, analyzer1: Audfprint_peaks, analyzer2: Audfprint_peaks) -> Dict[str, float]:
+    """audfprint_exps.py:30-84, one query file at a time through Matcher.file_match_to_msgs."""
+    from ..afp.audfprint.audfprint_match import Matcher
+    from ..afp.audfprint.hash_table import HashTable
+    hash_tab = HashTable(dbpath, device=analyzer1.device)
+    matcher = Matcher()
+    acc_no_den = acc_den = acc_mix = 0
+    for filename in files:
+        gt = filename.split("/")[-1].split(".")[0]
+        msgs1 = matcher.file_match_to_msgs(analyzer1, hash_tab, filename)
+        msgs2 = matcher.file_match_to_msgs(analyzer2, hash_tab, filename)
+        pred1 = msgs1[1].split("/")[-1].split(".")[0]
+        if msgs1[0] == "MATCH" and str(gt) == str(pred1):
+            acc_no_den += 1
+        pred2 = msgs2[1].split("/")[-1].split(".")[0]
+        if msgs2[0] == "MATCH" and str(gt) == str(pred2):
+            acc_den += 1
+        if msgs1[2] >= msgs2[2]:
+            pred_mix, message = pred1, msgs1[0]
+        else:
+            pred_mix, message = pred2, msgs2[0]
+        if message == "MATCH" and str(gt) == str(pred_mix):
+            acc_mix += 1
+    return {"No Denoising": acc_no_den / len(files), "With Denoising": acc_den / len(files), "Mix Pipeline": acc_mix / len(files)}

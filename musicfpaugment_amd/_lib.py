@@ -7,6 +7,7 @@ are then enqueued on torch's current stream and operate on torch allocations.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from ctypes import c_double, c_float, c_int, c_longlong, c_uint, c_ulonglong, c_void_p
@@ -301,6 +302,69 @@ def ptr(t) -> int:
 def stream() -> int:
     """HIP stream handle of torch's current stream on the current device (ptr() checks that every operand lives there)."""
     return torch.cuda.current_stream().cuda_stream
+
+
+# ----------------------------------------------------------------------------- launch timing (bench.py's roofline legs)
+class KernelTimer:
+    """Optional HIP-event stopwatch around the MFMA convolution launches (bench.py's roofline leg).
+    Events are recorded on the stream the kernels are launched on (torch's current stream)."""
+
+    def __init__(self, every: int = 1):
+        """`every` > 1: only every `every`-th step (begin_step() calls) is timed -- an event pair costs 6-10 us of stream time around each launch
+        (67 launches per train step: 0.4 ms of a 32 ms step), and the average launch duration does not need every step."""
+        self.pairs = []
+        self.every = max(1, int(every))
+        self.steps = 0           # begin_step() calls
+        self.sampled = 0         # ... of which timed
+        self._on = True
+
+    def begin_step(self):
+        self._on = (self.steps % self.every) == 0
+        self.steps += 1
+        self.sampled += int(self._on)
+
+    def start(self):
+        if not self._on:
+            return None
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+
+    def stop(self, e0):
+        e1 = torch.cuda.Event(enable_timing=True)
+        e1.record()
+        self.pairs.append((e0, e1))
+
+    def total_ms(self) -> float:
+        """Milliseconds inside the timed launches, scaled from the sampled steps to all steps (factor 1 without begin_step())."""
+        raw = float(sum(a.elapsed_time(b) for a, b in self.pairs))
+        return raw * (self.steps / self.sampled) if self.sampled else raw
+
+    def launches(self) -> int:
+        return len(self.pairs)
+
+
+_TIMER = None
+
+
+def set_timer(timer):
+    global _TIMER
+    _TIMER = timer
+
+
+@contextlib.contextmanager
+def timed():
+    """`with timed(): <launches>` -- the block is ONE timed launch of the active KernelTimer (set_timer); launches inside it are not
+    timed on their own."""
+    global _TIMER
+    t0 = _TIMER.start() if _TIMER is not None else None
+    timer, _TIMER = _TIMER, None
+    try:
+        yield
+    finally:
+        _TIMER = timer
+    if t0 is not None:
+        timer.stop(t0)
 
 
 def require_gpu(t, name="input"):

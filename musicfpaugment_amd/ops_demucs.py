@@ -10,8 +10,7 @@ from typing import Dict
 
 import torch
 
-from . import ops_unet as _K
-from ._lib import GemmDesc, check, lib, ptr, stream
+from ._lib import GemmDesc, check, lib, ptr, stream, timed
 
 DEPTH, KERNEL, STRIDE, RESAMPLE, FLOOR, ZEROS = 5, 8, 4, 4, 1e-3, 56
 
@@ -165,10 +164,8 @@ def gemm(A: int, lda, strideA, batch, M, W, bias, N, C: int, ldc, strideC, *, mo
                  C2=C2, ldc2=ldc2, strideC2=strideC2)
     if c1 is not None:                 # (x (B, Lin), w (8, K), b (K)): A is the first encoder layer, computed in the loader
         d.c1_x, d.c1_lin, d.c1_w, d.c1_b = ptr(c1[0]), c1[0].shape[1], ptr(c1[1]), ptr(c1[2])
-    t0 = _K._TIMER.start() if _K._TIMER is not None else None
-    check(lib().mfpa_gemm_mfma(ctypes.byref(d), stream()), "mfpa_gemm_mfma")
-    if t0 is not None:
-        _K._TIMER.stop(t0)
+    with timed():
+        check(lib().mfpa_gemm_mfma(ctypes.byref(d), stream()), "mfpa_gemm_mfma")
 
 
 
@@ -355,9 +352,7 @@ def lstm_two_layers(x: torch.Tensor, skip: torch.Tensor, wih, bias, whh_grouped,
     cs = [new(B, Tn, H), new(B, Tn, H)] if train else [None, None]
     cstate = [None, None] if train else [new(B, H), new(B, H)]
     xsum = new(B, Tn, H)
-    t0ev = _K._TIMER.start() if _K._TIMER is not None else None        # projection + recurrence of both layers as one timed group
-    timer, _K._TIMER = _K._TIMER, None
-    try:
+    with timed():                                                      # projection + recurrence of both layers as one timed group
         gemm(_p(x), H, 0, 1, B * Tn, wih[0], bias[0], 4 * H, _p(xp[0]), 4 * H, 0, precision=precision)
 
         work = [_lstm_work(dev, k, B, H) for k in range(2)] if PERSISTENT_LSTM else None
@@ -400,10 +395,6 @@ def lstm_two_layers(x: torch.Tensor, skip: torch.Tensor, wih, bias, whh_grouped,
                     project(a, b)
                     layer(1, a, b)
             main.wait_stream(side)
-    finally:
-        _K._TIMER = timer
-    if t0ev is not None:
-        _K._TIMER.stop(t0ev)
     if work is not None:
         lstm_mark(dev)                       # both layers are ordered before this point of the current stream (main.wait_stream(side))
     return xsum, [(x, xp[0], hs[0], cs[0]), (hs[0], xp[1], hs[1], cs[1])]
@@ -445,11 +436,9 @@ def _demucs_forward(pw: Dict[str, torch.Tensor], wav: torch.Tensor, precision: i
             # (12 MB per clip) is never written
             h = new(B, Lout, C)
             if FUSE_FIRST_LEVEL and precision == 1 and C == 48 and Lin % 4 == 0:   # one workgroup per 128 rows owns all packed GLU columns
-                t0 = _K._TIMER.start() if _K._TIMER is not None else None      # counted with the GEMM family (bench.py's roofline block)
-                check(L.mfpa_conv1d_c1_glu(ptr(x), B, Lin, Lout, C, ptr(pw["enc0.w"]), ptr(pw["enc0.b"]), ptr(pw["enc0.gw"]),
-                                           ptr(pw["enc0.gb"]), ptr(h), stream()), "mfpa_conv1d_c1_glu")
-                if t0 is not None:
-                    _K._TIMER.stop(t0)
+                with timed():                # counted with the GEMM family (bench.py's roofline block)
+                    check(L.mfpa_conv1d_c1_glu(ptr(x), B, Lin, Lout, C, ptr(pw["enc0.w"]), ptr(pw["enc0.b"]), ptr(pw["enc0.gw"]),
+                                               ptr(pw["enc0.gb"]), ptr(h), stream()), "mfpa_conv1d_c1_glu")
             else:
                 gemm_p(0, C, Lout * C, B, Lout, pw["enc0.gw"], pw["enc0.gb"], C, _p(h), C, Lout * C, mode=1,
                        c1=(x, pw["enc0.w"], pw["enc0.b"]))
@@ -477,11 +466,9 @@ def _demucs_forward(pw: Dict[str, torch.Tensor], wav: torch.Tensor, precision: i
         C = chans[DEPTH - 1 - d]
         if d == DEPTH - 1 and FUSE_LAST_LEVEL and precision == 1 and C == 48:
             y = new(B, 4 * (Lcur + 1))                           # 1x1 + GLU + ConvTranspose1d(48 -> 1) without the GLU output in memory
-            t0 = _K._TIMER.start() if _K._TIMER is not None else None
-            check(L.mfpa_glu_convT1d_c1(ptr(x), B, Lcur, C, ptr(pw[f"dec{d}.gw"]), ptr(pw[f"dec{d}.gb"]), ptr(pw["decL.w"]), pw["decL.b"],
-                                        ptr(y), stream()), "mfpa_glu_convT1d_c1")
-            if t0 is not None:
-                _K._TIMER.stop(t0)
+            with timed():
+                check(L.mfpa_glu_convT1d_c1(ptr(x), B, Lcur, C, ptr(pw[f"dec{d}.gw"]), ptr(pw[f"dec{d}.gb"]), ptr(pw["decL.w"]), pw["decL.b"],
+                                            ptr(y), stream()), "mfpa_glu_convT1d_c1")
             x, Lcur = y, 4 * (Lcur + 1)
             break
         if _PAD_ROWS_ONLY:

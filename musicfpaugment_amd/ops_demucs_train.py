@@ -26,8 +26,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import ops_demucs as D
-from . import ops_unet as _K
-from ._lib import GemmTnDesc, check, lib, ptr, stream
+from ._lib import GemmTnDesc, check, lib, ptr, stream, timed
 
 DEPTH, KERNEL, STRIDE, FLOOR = D.DEPTH, D.KERNEL, D.STRIDE, D.FLOOR
 HID = 48
@@ -56,10 +55,8 @@ def gemm_tn(A: int, lda, strideA, Bm: int, ldb, strideB, C: torch.Tensor, ldc, b
     colsum (M): += the column sums of A over all rows (the bias gradient), computed from the tiles the kernel stages anyway."""
     d = GemmTnDesc(A=A, lda=lda, strideA=strideA, Bm=Bm, ldb=ldb, strideB=strideB, C=ptr(C), ldc=ldc, batch=batch, R=R, M=M, N=N,
                    colsum=ptr(colsum), precision=WGRAD_PRECISION if precision is None else precision)
-    t0 = _K._TIMER.start() if _K._TIMER is not None else None
-    check(lib().mfpa_gemm_tn(ctypes.byref(d), stream()), "mfpa_gemm_tn")
-    if t0 is not None:
-        _K._TIMER.stop(t0)
+    with timed():
+        check(lib().mfpa_gemm_tn(ctypes.byref(d), stream()), "mfpa_gemm_tn")
 
 
 def colsum(x: int, rows, C, ld, out: torch.Tensor):
@@ -442,30 +439,27 @@ class DemucsTrainEngine:
         Tn = S["Tn"]
         (seq0, g0, hseq0, cseq0), (seq1, g1, hseq1, cseq1) = S["lstm"]
         dc0, dc1, dx1 = new(B, H), new(B, H), new(B, Tn, H)
-        t0 = _K._TIMER.start() if _K._TIMER is not None else None
-        timer, _K._TIMER = _K._TIMER, None
+        with timed():
+            pipelined = D.PIPELINE_LSTM and D.PIPELINE_LSTM_BWD and Tn > D.LSTM_CHUNK and B <= D.PIPELINE_MAX_CLIPS
+            # two persistent launches run side by side in the chunked pipeline: each may keep half the CUs' worth of workgroups resident
+            wg_budget = torch.cuda.get_device_properties(dev).multi_processor_count // 2 if pipelined else 0
+            bwork = {id(g1): D._lstm_work(dev, 1, B, H, backward=True), id(g0): D._lstm_work(dev, 0, B, H, backward=True)} if D.PERSISTENT_LSTM_BWD else None
 
-        pipelined = D.PIPELINE_LSTM and D.PIPELINE_LSTM_BWD and Tn > D.LSTM_CHUNK and B <= D.PIPELINE_MAX_CLIPS
-        # two persistent launches run side by side in the chunked pipeline: each may keep half the CUs' worth of workgroups resident
-        wg_budget = torch.cuda.get_device_properties(dev).multi_processor_count // 2 if pipelined else 0
-        bwork = {id(g1): D._lstm_work(dev, 1, B, H, backward=True), id(g0): D._lstm_work(dev, 0, B, H, backward=True)} if D.PERSISTENT_LSTM_BWD else None
+            bwgs = D.lstm_seq_workgroups(B, H, wg_budget, backward=True) if bwork is not None else 0
 
-        bwgs = D.lstm_seq_workgroups(B, H, wg_budget, backward=True) if bwork is not None else 0
+            def bwd(whhT, gates, cseq, dhout, dc, a, b):
+                if bwork is not None:            # one persistent launch for the range (csrc/demucs_train.hip: lstm_bwd_seq_kernel)
+                    done = D._GUARD.admit(dev, bwgs)
+                    check(L.mfpa_lstm_layer_bwd_seq(ptr(whhT), ptr(gates), ptr(cseq), ptr(dhout), ptr(dc), B, Tn, H, a, b, wg_budget,
+                                                    ptr(bwork[id(gates)]), stream()), "mfpa_lstm_layer_bwd_seq")
+                    done()
+                    return
+                check(L.mfpa_lstm_layer_bwd_range(ptr(whhT), ptr(gates), ptr(cseq), ptr(dhout), ptr(dc), B, Tn, H, a, b, stream()),
+                      "mfpa_lstm_layer_bwd_range")
 
-        def bwd(whhT, gates, cseq, dhout, dc, a, b):
-            if bwork is not None:            # one persistent launch for the range (csrc/demucs_train.hip: lstm_bwd_seq_kernel)
-                done = D._GUARD.admit(dev, bwgs)
-                check(L.mfpa_lstm_layer_bwd_seq(ptr(whhT), ptr(gates), ptr(cseq), ptr(dhout), ptr(dc), B, Tn, H, a, b, wg_budget,
-                                                ptr(bwork[id(gates)]), stream()), "mfpa_lstm_layer_bwd_seq")
-                done()
-                return
-            check(L.mfpa_lstm_layer_bwd_range(ptr(whhT), ptr(gates), ptr(cseq), ptr(dhout), ptr(dc), B, Tn, H, a, b, stream()),
-                  "mfpa_lstm_layer_bwd_range")
+            def dx_chunk(a, b):                                              # dL/d(h0)[:, a:b] = dgates1[:, a:b] W_ih1
+                D.gemm(_p(g1, a * 4 * H), 4 * H, Tn * 4 * H, B, b - a, W["lstm1.wihT"], None, H, _p(dx1, a * H), H, Tn * H, precision=prec)
 
-        def dx_chunk(a, b):                                              # dL/d(h0)[:, a:b] = dgates1[:, a:b] W_ih1
-            D.gemm(_p(g1, a * 4 * H), 4 * H, Tn * 4 * H, B, b - a, W["lstm1.wihT"], None, H, _p(dx1, a * H), H, Tn * H, precision=prec)
-
-        try:
             if not pipelined:
                 bwd(W["lstm1.whhT"], g1, cseq1, dxsum, dc1, 0, Tn)
                 dx_chunk(0, Tn)
@@ -484,10 +478,6 @@ class DemucsTrainEngine:
                         dx_chunk(a, b)
                         bwd(W["lstm0.whhT"], g0, cseq0, dx1, dc0, a, b)
                 main.wait_stream(side)
-        finally:
-            _K._TIMER = timer
-        if t0 is not None:
-            _K._TIMER.stop(t0)
         if bwork is not None:
             D.lstm_mark(dev)                 # the error words of this step's persistent launches, copied right behind the recurrence
         for layer, (seq, gates, hseq) in enumerate(((seq0, g0, hseq0), (seq1, g1, hseq1))):

@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from ._lib import ConvDesc, PackJob, WgradDesc, check, lib, ptr, stream
+from ._lib import ConvDesc, PackJob, WgradDesc, check, lib, ptr, stream, timed
 from . import ops_unet as K
 
 BN_EPS = 1e-5
@@ -245,10 +245,8 @@ def conv_mfma(x0, w, Cout, *, mode=0, in_affine: Optional[Stats] = None, x1=None
                  bwd_z_is_bf16=int(bool(bwd_of) and part is not None and bwd_of[0].dtype == torch.bfloat16))
     if in16 and not ((plain and w_layout == 2 and mode == 0) or (mode == 1 and precision == 1)):
         raise ValueError("bfloat16 sources need the plain-bf16 conv_wd16_kernel (precision 2, w_layout 2) or the bf16x3 transposed convolution")
-    t0 = K._TIMER.start() if K._TIMER is not None else None
-    check(lib().mfpa_conv_mfma(ctypes.byref(d), stream()), "mfpa_conv_mfma")
-    if t0 is not None:
-        K._TIMER.stop(t0)
+    with timed():
+        check(lib().mfpa_conv_mfma(ctypes.byref(d), stream()), "mfpa_conv_mfma")
     return y
 
 
@@ -307,10 +305,8 @@ def wgrad_mfma(dz, x0, dw, Cout, *, mode=0, in_affine: Optional[Stats] = None, x
                   W1=0 if x1 is None else x1.shape[2], B=B, H=H, W=W, Cout=Cout, mode=mode,
                   drop_seed=_drop(in_affine)[0], drop_thresh=_drop(in_affine)[1], drop_scale=_drop(in_affine)[2],
                   precision=precision)
-    t0 = K._TIMER.start() if K._TIMER is not None else None
-    check(lib().mfpa_wgrad_mfma(ctypes.byref(d), stream()), "mfpa_wgrad_mfma")
-    if t0 is not None:
-        K._TIMER.stop(t0)
+    with timed():
+        check(lib().mfpa_wgrad_mfma(ctypes.byref(d), stream()), "mfpa_wgrad_mfma")
 
 
 def _npix(t):

@@ -146,8 +146,8 @@ class UNet(nn.Module):
         return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
 
     def packed_weights(self) -> Dict[str, torch.Tensor]:
-        """Kernel-layout weights ([tap][Cout][Cin]) + folded eval BatchNorm; rebuilt when parameters change."""
-        key = (self._weights_key(), self.precision)
+        """Kernel-layout weights ([tap][Cout][Cin]) + folded eval BatchNorm; rebuilt when the parameters or what gets packed change."""
+        key = (self._weights_key(), self.precision, K.FOLD_UP, tuple(K.FOLD_UP_LEVELS), K.FOLD_UP_FP32)
         if self._packed is None or key != self._packed_key:
             self._packed = K.pack_unet_weights(self.state_dict(), self.precision)
             self._packed_key = key

@@ -439,3 +439,26 @@ def test_split_layout_between_wave_specialised_convolutions():
     wk = K.pack_conv3x3(torch.randn(128, 512, 3, 3, generator=g) / 60.0).cuda()
     with pytest.raises(ValueError):
         K.conv3x3_fused(xs, K.split_bf16x3(wk), torch.ones(128).cuda(), torch.zeros(128).cuda(), precision=1, wf=(2, K.split_bf16x3_frag(wk, 2)), x0_split=True)
+
+
+def test_plan_split_edges_at_the_headline_shape():
+    """unet_plan's split edges at 257 x 251, bf16x3, as the hand-written per-edge conditions of the forward chose them (recorded from
+    that code's launches on the MI355X).  With up4 folded its two edges (inc -> up4.0, up4.0 -> up4.3) are plain float32; the three
+    encoder edges follow the launches on conv_ws64_kernel."""
+    from musicfpaugment_amd import ops_unet as K
+    if K.frag_layout() != 2:
+        pytest.skip("the library was built without the 16 x 16 x 32 weights-direct kernels")
+    d1, d2 = "down1.maxpool_conv.1.double_conv", "down2.maxpool_conv.1.double_conv"
+    encoder = {("inc.double_conv.3", "pool_split"), (d1 + ".0", "x0_split"), (d1 + ".0", "y_split"), (d1 + ".3", "x0_split"),
+               (d1 + ".3", "pool_split"), (d2 + ".0", "x0_split")}
+    up4 = {("inc.double_conv.3", "y_split"), ("up4.conv.double_conv.0", "x0_split"), ("up4.conv.double_conv.0", "y_split"),
+           ("up4.conv.double_conv.3", "x0_split")}
+    for fold, want in ((True, encoder), (False, encoder | up4)):
+        K.FOLD_UP = fold
+        try:
+            plan = K.unet_plan(257, 251, 1)
+        finally:
+            K.FOLD_UP = True
+        got = {(key, f) for key, st in plan.items() for f in ("x0_split", "y_split", "pool_split") if getattr(st, f)}
+        assert got == want, (fold, sorted(got ^ want))
+        assert ("up4.conv.double_conv.0" in plan) != fold

@@ -206,3 +206,39 @@ def test_upconv_fused_border_geometry_sweep():
                 assert relative_l1(got, want) < tol, (H, W, Hl, Wl, prec)
                 for sl in (np.s_[:, :, 0], np.s_[:, :, -1], np.s_[:, :, :, 0], np.s_[:, :, :, -1]):
                     assert relative_l1(got[sl], want[sl]) < 3 * tol, (H, W, Hl, Wl, prec, sl)
+
+
+def test_flipping_fold_up_on_a_live_module_repacks_and_reroutes():
+    """UNet.packed_weights keys on the switches that change what is packed: turning FOLD_UP off on a module already packed with it on
+    drops the mfpa_upconv_fused operands, packs the two-launch images instead and routes every level through mfpa_convT2x2 -- and back."""
+    from musicfpaugment_amd import ops_unet as K
+    from musicfpaugment_amd.training.unet import UNet
+    from musicfpaugment_amd.training.weights import formula_state_dict
+    m = UNet(1, 1, rate=0.05)
+    m.load_state_dict(formula_state_dict(0))
+    m = m.cuda().eval()
+    m.precision = 1
+    x = torch.rand(2, 1, 257, 251, device="cuda")
+    lay = K.frag_layout()
+    try:
+        counts = {}
+        for fold in (True, False, True):
+            K.FOLD_UP = fold
+            pw = m.packed_weights()
+            assert ("up4.upc.wup" in pw) == fold
+            assert (("up4.conv.double_conv.0", lay, False) in pw["images"]) != fold and (("up4.up", 0, False) in pw["images"]) != fold
+            timer = K.KernelTimer()
+            K.set_timer(timer)
+            try:
+                y = m(x)
+            finally:
+                K.set_timer(None)
+            torch.cuda.synchronize()
+            counts.setdefault(fold, []).append((timer.launches(), y.cpu()))
+        (n_on, y_on), (n_again, y_again) = counts[True]
+        n_off, y_off = counts[False][0]
+        assert n_off == n_on + len(K.FOLD_UP_LEVELS)                # one more launch per level: the transposed convolution
+        assert n_again == n_on and torch.equal(y_again, y_on)
+        assert float((y_on - y_off).abs().max()) <= 1e-4 * float(y_on.abs().max())
+    finally:
+        K.FOLD_UP = True

@@ -290,11 +290,10 @@ typedef struct mfpa_conv_desc {
   const float* c1_x32; const double* c1_spec64; const double* c1_denom;
   const float* c1_w; const float* c1_scale; const float* c1_shift;
   /* precision 1, mode 0: which bf16x3 image `w` holds.  0 = the row image ([tap][Cin / 32][Cout][128 B], staged through LDS);
-   * 1, 2 = FRAGMENT-ORDERED images of the weights-direct kernels (a wave reads the MFMA weight operand of its column tile straight
-   * from L1 / L2: no weight tile in LDS, one barrier per 32-channel chunk instead of one per tap): 2 = [tap][Cin / 32][Cout / 16]
-   * [hi | lo][lane 64][16 B] for v_mfma_f32_16x16x32_bf16 (conv_wd16_kernel), 1 = [tap][Cin / 32][Cout / 32][substep 2][hi | lo]
-   * [lane 64][16 B] for v_mfma_f32_32x32x16_bf16 -- valid exactly where mfpa_conv_weight_layout() returns that number,
-   * MFPA_EINVAL otherwise. */
+   * 2 = the FRAGMENT-ORDERED image of the weights-direct kernels (a wave reads the MFMA weight operand of its column tile straight
+   * from L1 / L2: no weight tile in LDS, one barrier per 32-channel chunk instead of one per tap): [tap][Cin / 32][Cout / 16]
+   * [hi | lo][lane 64][16 B] for v_mfma_f32_16x16x32_bf16 (conv_ws64_kernel, conv_wd16_kernel) -- valid exactly where
+   * mfpa_conv_weight_layout() returns 2, MFPA_EINVAL otherwise.  Any other value is MFPA_EINVAL. */
   int w_layout;
   /* w_layout 2, mode 0, optional (training forward): a bf16 copy of source 0 AS THE CONVOLUTION SAW IT (in_scale0 / in_shift0 / ReLU /
    * dropout applied), (B,H,W,C0), written by the halo loader of the first output-channel tile -- the operand mfpa_wgrad_mfma(precision 3)
@@ -332,7 +331,7 @@ typedef struct mfpa_conv_desc {
   int bwd_z_is_bf16;
 } mfpa_conv_desc;
 int mfpa_conv_mfma(const mfpa_conv_desc* d, void* stream);
-/* HOST function: the w_layout (0, 1 or 2) the fastest kernel for a (H, W) convolution of this shape reads. */
+/* HOST function: the w_layout (0 or 2) the fastest kernel for a (H, W) convolution of this shape reads. */
 int mfpa_conv_weight_layout(int H, int W, int Cin, int Cout, int mode, int precision);
 /* HOST function (round 5): 1 if the INFERENCE launch of this 3x3 shape (precision 1, w_layout 2, no on-load affine, no training side
  * output) runs on conv_ws64_kernel, whose epilogue is cheapest when the output scale is already IN the weights: pass out_scale = NULL
@@ -540,16 +539,16 @@ int mfpa_l1_loss(const float* pred, const double* target, long long n, float* dp
 /* Operand image of a convolution's weights, rebuilt from the master fp32 parameters after every optimiser step (replaces the
  * host-side flip / transpose / bf16 split of the packing code).  w: [taps][Co][Ci] fp32.  out, precision 0: [taps][nrows][K] float rows;
  * precision 1: the bf16x3 image [taps][K / 32][nrows][128 B], a row = 32 bf16 hi | 32 bf16 lo in eight 16-byte slots stored at slot
- * index (logical ^ ((row >> 1) & 7)) -- a (tap, chunk, 128-row) tile is 16 KB contiguous (csrc/unet.hip); precision 2: the same split in
- * the FRAGMENT-ORDERED layout of mfpa_conv_desc.w_layout = 1 ([taps][K / 32][nrows / 32][substep][hi | lo][lane][8 bf16]); precision 3:
- * that of w_layout = 2 ([taps][K / 32][nrows / 16][hi | lo][lane][8 bf16]).  flip_transpose = 0: rows = output
+ * index (logical ^ ((row >> 1) & 7)) -- a (tap, chunk, 128-row) tile is 16 KB contiguous (csrc/unet.hip); precision 3: the same split in
+ * the FRAGMENT-ORDERED layout of mfpa_conv_desc.w_layout = 2 ([taps][K / 32][nrows / 16][hi | lo][lane][8 bf16]); precision 2 (the
+ * image of the retired w_layout 1) is MFPA_EINVAL, and the codes stay numbered 1 + w_layout.  flip_transpose = 0: rows = output
  * channels row0 .. row0+nrows-1, K = Ci (forward operand).  flip_transpose = 1: rows = input channels row0 .. row0+nrows-1,
  * K = Co, and for taps == 9 the kernel is flipped (tap t <- 8 - t): the input-gradient operand (training/unet.py's Conv2d /
  * ConvTranspose2d backward).  Co, Ci, row0, nrows multiples of 32. */
 int mfpa_pack_conv_weights(const float* w, int taps, int Co, int Ci, int flip_transpose, int row0, int nrows, int precision,
                            float* out, void* stream);
 /* Every operand image a training step needs, in ONE launch (round 5): `jobs_dev` = `njobs` of these in DEVICE memory, each the argument set of
- * one mfpa_pack_conv_weights call (same checks apply; the caller validates) plus tile0 = the number of 32 x 32 tiles of all jobs before it
+ * one mfpa_pack_conv_weights call (same checks apply, precision 2 included; the caller validates) plus tile0 = the number of 32 x 32 tiles of all jobs before it
  * (a job has (K / 32) * (nrows / 32) * taps tiles, K = flip_transpose ? Co : Ci); total_tiles = their sum.  Pointers and shapes of a
  * training engine never change, so the table is built once and the launch repeated after every optimiser step. */
 typedef struct mfpa_pack_job {

@@ -21,7 +21,7 @@ EINVAL = -22
 EHIP = -1000
 F32, F64 = 0, 1
 STFT_TABLE_LEN = 1288
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 
 class MfpaError(RuntimeError):

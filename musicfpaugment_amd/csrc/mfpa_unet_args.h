@@ -24,7 +24,7 @@ struct ConvArgs {
   const float* w1x1;                 // optional fused OutConv 1x1 to one class (needs the whole Cout in one workgroup):
   float b1x1;                        //   y1x1[pixel] = sum_c out[pixel][c] * w1x1[c] + b1x1
   float* y1x1;
-  int w_frag;                        // 1: `w` is the fragment-ordered bf16x3 image of the BDIR kernels (mfpa_conv_desc.w_layout)
+  int w_frag;                        // 2: `w` is the fragment-ordered bf16x3 image of the weights-direct kernels (mfpa_conv_desc.w_layout), 0: the row image
   int in16;                          // conv_wd16_kernel (plain) / convT_mfma_kernel: the sources are bfloat16 tensors (mfpa_conv_desc.x0_is_bf16)
   int x0_split, x1_split, y_split, y_pool_split;   // conv_ws64_kernel: tensors in the split layout ([32 bf16 hi | 32 bf16 lo] per 32-channel chunk; mfpa_conv_desc)
   int plain;                         // conv_wd16_kernel: plain bf16 products (hi halves only: mfpa_conv_desc.precision 2, the training step)

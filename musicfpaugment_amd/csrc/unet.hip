@@ -44,63 +44,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef MFPA_WD16_PERSIST_PLAIN
-#define MFPA_WD16_PERSIST_PLAIN 1  // the same for the plain-bf16 (training) instantiations, whose MFMA time is a third: prologue / epilogue weigh three times more
-#endif
-#ifndef MFPA_WD16_PERSIST_ROWS
-#define MFPA_WD16_PERSIST_ROWS 0   // the same for the ROWS inference form (A/B builds)
-#endif
-#ifndef MFPA_WD16_PERSIST2
-#define MFPA_WD16_PERSIST2 1  // conv_wd16_kernel<.., WMW = 2>, tap-by-tap inference form: persistent tile loop like the 64-channel form (0: one tile per workgroup, A/B builds)
-#endif
-#ifndef MFPA_HALO_SPREAD
-#define MFPA_HALO_SPREAD 0    // conv_wd16_kernel<.., WMW = 4>: staging slot k of the next chunk's halo requested at tap k (1) instead of all at tap 0 (A/B builds)
-#endif
-#ifndef MFPA_EPI_LDS
-#define MFPA_EPI_LDS 1        // conv_wd16_kernel: the epilogue's per-channel constants from an LDS copy (0: global loads inside the epilogue, A/B builds)
-#endif
-#ifndef MFPA_CONV_PIPE
-#define MFPA_CONV_PIPE 1      // 0: the round-1 main loop for the bf16x3 3x3 convolution too (A/B builds of tools/)
-#endif
-#ifndef MFPA_CONV_BIG_MIN_CIN
-#define MFPA_CONV_BIG_MIN_CIN 64    // 128-channel tiles: the 8-wave 256-pixel shape from this many input channels on (256: round 1's choice)
-#endif
-#ifndef MFPA_CONV_PIPE4
-#define MFPA_CONV_PIPE4 0     // 1: the pipelined loop also for the 4-wave 256 x 64 shape, one wave per SIMD (A/B builds)
-#endif
-#ifndef MFPA_CONV_PIPE_COND_A
-#define MFPA_CONV_PIPE_COND_A 0   // 1: the pipelined loop skips halo slots outside the image too (A/B builds)
-#endif
-#ifndef MFPA_CONV_WN64
-#define MFPA_CONV_WN64 1
-#endif
-#ifndef MFPA_CONV_STATIC_TAPS
-#define MFPA_CONV_STATIC_TAPS 1     // 3x3 plain loop with compile-time taps (0: one runtime (chunk, tap) iteration, round 1's form)
-#endif
-#ifndef MFPA_CONV_MT4
-#define MFPA_CONV_MT4 0             // 1: the 256 x 128 tile on FOUR waves of 128 px x 64 ch (8 x 32 patches); 2: also the 16 x 16 patches of the bottleneck
-                                    // (measured per layer: 3-17 % SLOWER than the 8-wave shape -- a quarter less LDS traffic does not pay for one wave per SIMD)
-#endif
-#ifndef MFPA_CONV_LDS_EPI
-#define MFPA_CONV_LDS_EPI 0         // 1: 64-channel tiles of the plain loop write their output (and the fused max-pool) through LDS as 16-byte pieces.
-                                    // Correct (all GPU tests pass with it) and the in-kernel timeline shows the epilogue shrink 7.8 -> 5.6-6.3 us per
-                                    // workgroup, but three same-call A/B pairs read 4082 / 4088 / 4091 vs 4091 / 4090 / 4093 clips/s: the stores of one
-                                    // workgroup already overlap the partner workgroup's loop -- off.
-#endif
-#ifndef MFPA_CONV_WD16
-#define MFPA_CONV_WD16 1            // >= 128-channel weights-direct layers on v_mfma_f32_16x16x32_bf16 (0: the 32 x 32 x 16 BDIR form of round 3's first half)
-#endif
-#ifndef MFPA_CONV_BDIR64
-#define MFPA_CONV_BDIR64 0          // 1: weights-direct form also for 64-channel output tiles (8 waves of 64 px x 32 ch, one workgroup per CU): correct
-                                    // (tests/test_gpu_unet.py runs it when enabled), +1.7 % per layer stand-alone but -2.8 % on the headline (3990 vs 4107 clips/s, two A/B pairs)
-#endif
-#ifndef MFPA_BDIR_SPREAD_SPLIT
-#define MFPA_BDIR_SPREAD_SPLIT 1    // weights-direct kernels: the halo split one staging slot per tap inside the MFMA phases (0: one block at tap 2)
-#endif
-#ifndef MFPA_CONV_BOTTLENECK8
-#define MFPA_CONV_BOTTLENECK8 1     // the 16x15 level on the 8-wave shape with 16x16-pixel patches (0: round 1's 4-wave 8x16 shape)
-#endif
-
 // PREC 1 weight image ("w3", built by ops_unet.split_bf16x3 / mfpa_pack_conv_weights): [tap][chunk][row][128 B], one row =
 // the 32 channels of a chunk as 8 slots of 16 B, logical slots 0-3 = 32 bf16 hi, 4-7 = 32 bf16 lo, stored at PHYSICAL slot
 // (logical ^ ((row >> 1) & 7)).  A (tap, chunk, 128-row) tile is 16 KB contiguous and is copied verbatim into LDS by LDS-DMA
@@ -132,18 +75,15 @@ constexpr int pin_read_slots(int slots, int left) {      // how many MFMAs pin_r
   return used;
 }
 
-// does this instantiation run the software-pipelined main loop (one workgroup per CU, two halo stages)?
-constexpr bool conv_is_pipe(int BN, int PH, int PW, int WM, int WN, int MODE, int PREC, int MT = 2) {
-  return (MFPA_CONV_PIPE != 0) && MODE == 0 && PREC == 1 &&
-         (WM * WN * MT == 16 || (MFPA_CONV_PIPE4 != 0 && WM * WN == 4 && BN == 64 && PH * PW == 256));
-}
+// does this instantiation run the software-pipelined main loop (the bf16x3 3x3 convolution on 8 waves: one workgroup per CU, two
+// halo stages)?
+constexpr bool conv_is_pipe(int WM, int WN, int MODE, int PREC) { return MODE == 0 && PREC == 1 && WM * WN == 8; }
 
 using mfpa_unet::ConvArgs;     // csrc/mfpa_unet_args.h (shared with csrc/unet_ws.hip)
 
 // MODE 0: 3x3 conv, pad 1 (9 taps, halo 1).
-// MODE 1: 2x2 stride-2 transposed conv forward: one tap per workgroup column
-//         (blockIdx.y = tap * (Cout/BN) + n-tile), output scattered to (2y+dy, 2x+dx).
 // MODE 2: transposed-conv input gradient: 4 taps, A gathered from the (2H,2W) tensor at (2y+dy, 2x+dx).
+// (The transposed convolution's forward has its own kernel, convT_mfma_kernel.)
 // PREC 0: v_mfma_f32_32x32x2_f32 (exact fp32 products).
 // PREC 1: "bf16x3" -- every fp32 operand is split x = hi + lo into two bf16 values and the product is
 //         hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 (fp32 accumulate): 3 matrix instructions at 16x
@@ -158,27 +98,16 @@ using mfpa_unet::ConvArgs;     // csrc/mfpa_unet_args.h (shared with csrc/unet_w
 //     MFMA block of iteration it from As / Bs[it&1]
 //     one barrier                                 (+ barrier, halo store, at a chunk's last tap)
 // so weight loads have two MFMA blocks to land, and the only exposed cost per iteration is the wave skew.
-// MT_ = 32-pixel MFMA tiles per wave: 2 (a wave owns 64 pixels), or 4 -- 128 pixels x (BN / WN) channels per wave, FOUR waves for the
-// 256 x 128 tile, one per SIMD with the whole register file (256 VGPRs + 206 AGPRs, no scratch): 12 fragment reads per 24 MFMAs
-// instead of 16, a quarter less LDS traffic.  Measured 3-17 % slower per layer than two 64-pixel waves per SIMD (MFPA_CONV_MT4).
-// BDIR ("weights direct"): the pipelined loop with NO weight tile in LDS.  8 waves = WM 2 x WN 4, a wave owns 128 pixels x 32
-// channels (MT 4, NT 1): its B operand -- [2 substeps][hi, lo] fragments of ONE 32-channel column tile per (tap, chunk) -- comes
-// straight from L1 / L2 into the MFMA operand registers out of a FRAGMENT-ORDERED weight image ("wf": [tap][chunk][Cout / 32]
-// [substep][hi | lo][lane][16 B], built by ops_unet.split_bf16x3_frag; a wave-load is 1 KB contiguous), two iterations ahead
-// through a ring of three register sets.  What that buys: no weight staging (2 global loads + 2 ds_write_b128 per thread and
-// tap), no B-fragment LDS reads (the A side reads 8 ds_read_b128 per substep, as many as A + B did), and above all no barrier
-// per tap -- the only LDS hand-off left is the halo tile, one barrier per 32-channel chunk (nine taps).  The column tile is
-// fetched by the two waves that share it (wm 0 / 1): 32 KB per iteration through the CU's L1 instead of 16 KB.
-template <int BN, int PH, int PW, int WM, int WN, int MODE, int PREC, bool C1SRC = false, int MT_ = 2, bool BDIR = false>
-__global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH, PW, WM, WN, MODE, PREC, MT_)) ? 1 : 2) void conv_mfma_kernel(ConvArgs a) {
+template <int BN, int PH, int PW, int WM, int WN, int MODE, int PREC, bool C1SRC = false>
+__global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_kernel(ConvArgs a) {
+  static_assert(MODE == 0 || MODE == 2, "3x3 convolution or the transposed convolution's input gradient");
   constexpr int THREADS = 64 * WM * WN;
   constexpr int HALO = (MODE == 0) ? 1 : 0;
-  constexpr int TAPS = (MODE == 0) ? 9 : (MODE == 2 ? 4 : 1);
-  constexpr bool A_PER_TAP = (MODE == 2);               // A tile changes with the tap
+  constexpr int TAPS = (MODE == 0) ? 9 : 4;
   constexpr int HPW = PW + 2 * HALO, HPH = PH + 2 * HALO;
   constexpr int HP = HPW * HPH;                       // halo-tile pixels
   constexpr int BM = PH * PW;
-  constexpr int MT = MT_;
+  constexpr int MT = 2;                               // 32-pixel MFMA tiles per wave
   constexpr int WPX = 32 * MT;                        // pixels per wave
   static_assert(BM == WPX * WM, "workgroup tile is 32*MT*WM pixels");
   constexpr int NT = BN / (32 * WN);                  // 32-wide n tiles per wave
@@ -189,9 +118,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
   // PIPE (the bf16x3 3x3 convolution on the 8-wave shapes, one workgroup per CU): software-pipelined main loop with the halo
   // tile double-buffered in LDS, see step_pipe below.  The 4-wave shapes keep the plain loop: with 256 threads the staging
   // registers are twice as many per thread and the second fragment set spills (measured: 2x slower).
-  static_assert(!BDIR || (MODE == 0 && PREC == 1 && WM * WN == 8 && (MT_ == 4 || MT_ == 2) && BN == 32 * WN && !C1SRC),
-                "BDIR: 8 waves of (32 MT) px x 32 ch, bf16x3 3x3 convolution");
-  constexpr bool PIPE = BDIR || conv_is_pipe(BN, PH, PW, WM, WN, MODE, PREC, MT);
+  constexpr bool PIPE = conv_is_pipe(WM, WN, MODE, PREC);
   constexpr int A_STAGES = PIPE ? 2 : 1;
   // PIPE: a halo stage has a row for every staging slot (A_F4 * THREADS / 8 >= HP), so the split / store pass needs no tail
   // predicate: every halo load is consumed on every path and hipcc keeps no "maybe pending" state across iterations
@@ -199,10 +126,10 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* As = reinterpret_cast<float*>(smem);         // [A_STAGES][HPS][LDK]
-  constexpr int B_STAGES = BDIR ? 0 : 2, B_STAGE = BN * LDK;     // weight-tile stages: [2][BN][LDK] padded rows, written through registers (BDIR: none)
+  constexpr int B_STAGE = BN * LDK;                   // weight-tile stages: [2][BN][LDK] padded rows, written through registers
   float* Bs0 = As + A_STAGES * HPS * LDK;
   constexpr int SW = PW + 4, SH = PH + 4;             // C1SRC: spectrogram patch with a 2-pixel halo, then the (9, 64) weights
-  float* Sp = Bs0 + B_STAGES * B_STAGE;               // [SH][SW]
+  float* Sp = Bs0 + 2 * B_STAGE;                      // [SH][SW]
   float* W1s = Sp + SH * SW;                          // [9][64]
 
   MFPA_STAMP(0);
@@ -214,10 +141,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
   const int tx = bx % a.tiles_x; bx /= a.tiles_x;
   const int ty = bx % a.tiles_y; bx /= a.tiles_y;
   const int b = bx;
-  const int n_tiles = a.Cout / BN;
-  const int n_tile = (MODE == 1) ? blockIdx.y % n_tiles : blockIdx.y;
-  const int ct_tap = (MODE == 1) ? blockIdx.y / n_tiles : 0;
-  const int n0 = n_tile * BN;
+  const int n0 = blockIdx.y * BN;
   const int y0 = ty * PH, x0p = tx * PW;
   const int Cin = a.C0 + a.C1;
   const int nchunks = Cin / KC;
@@ -269,11 +193,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
         unsigned off;
         if (MODE == 2) off = ((unsigned)((2 * gy + (tap >> 1)) * (2 * a.W) + 2 * gx + (tap & 1)) * (unsigned)a.C0 + (unsigned)(c0 + 4 * aq)) * 4u;
         else off = ((unsigned)(gy * a.W + gx) * (unsigned)a.C0 + (unsigned)(c0 + 4 * aq)) * 4u;
-        if ((PIPE && !MFPA_CONV_PIPE_COND_A) || apix[it] >= 0) v = *reinterpret_cast<const f32x4*>(xb0 + off);
+        if (PIPE || apix[it] >= 0) v = *reinterpret_cast<const f32x4*>(xb0 + off);
       } else {
         const int y1 = min(max(gy - a.oy1, 0), a.H1 - 1), x1 = min(max(gx - a.ox1, 0), a.W1 - 1);
         const unsigned off = ((unsigned)(y1 * a.W1 + x1) * (unsigned)a.C1 + (unsigned)(c0 - a.C0 + 4 * aq)) * 4u;
-        if ((PIPE && !MFPA_CONV_PIPE_COND_A) || src1_inside(apix[it])) v = *reinterpret_cast<const f32x4*>(xb1 + off);
+        if (PIPE || src1_inside(apix[it])) v = *reinterpret_cast<const f32x4*>(xb1 + off);
       }
       areg[it] = v;
     }
@@ -364,10 +288,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
   auto load_b = [&](int it_flat, auto SET) __attribute__((always_inline)) {
     constexpr int set = decltype(SET)::value;
     const int chunk = it_flat / TAPS, tap = it_flat % TAPS;
-    const int wt = (MODE == 1) ? ct_tap : tap;
     // PREC 0: [tap][Cout][Cin] floats; PREC 1: the chunk-major swizzled image (header of this file)
-    const char* wbase = reinterpret_cast<const char*>((PREC == 0) ? a.w + ((size_t)wt * a.Cout + n0) * Cin + chunk * KC
-                                                                 : a.w + (((size_t)wt * nchunks + chunk) * a.Cout + n0) * KC);
+    const char* wbase = reinterpret_cast<const char*>((PREC == 0) ? a.w + ((size_t)tap * a.Cout + n0) * Cin + chunk * KC
+                                                                 : a.w + (((size_t)tap * nchunks + chunk) * a.Cout + n0) * KC);
 #pragma unroll
     for (int it = 0; it < B_F4; ++it)
       if (B_EXACT || tid + it * THREADS < BN * (KC / 4)) breg[set][it] = *reinterpret_cast<const f32x4*>(wbase + b_off[it]);
@@ -488,19 +411,16 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
 
   using Set0 = std::integral_constant<int, 0>;
   using Set1 = std::integral_constant<int, 1>;
-  // one pipeline iteration; register set CUR holds B(it+1), the other set receives B(it+2)
+  // one pipeline iteration of MODE 2, whose A tile changes with the tap; register set CUR holds B(it+1), the other set receives B(it+2)
   auto step = [&](int it, auto CUR) __attribute__((always_inline)) {
     constexpr int cur = decltype(CUR)::value;
-    const int tap = it % TAPS;
-    const bool chunk_end = (tap == TAPS - 1);
     if (!MFPA_EXP_FLAG(a.dbg, 1)) {
       if (it + 1 < nit) store_b(CUR, Bs0 + ((it + 1) & 1) * (BN * LDK));
       if (it + 2 < nit) load_b(it + 2, std::integral_constant<int, 1 - cur>{});
     }
-    if (!A_PER_TAP && tap == 0 && it + TAPS < nit) load_a(it / TAPS + 1, 0);   // next chunk's halo, a whole chunk ahead
-    if (A_PER_TAP && it + 1 < nit) load_a((it + 1) / TAPS, (it + 1) % TAPS);
-    if (!MFPA_EXP_FLAG(a.dbg, 8)) compute((MODE == 0) ? ((tap / 3) * HPW + (tap % 3)) * LDK : 0, Bs0 + (it & 1) * (BN * LDK));
-    if ((chunk_end || A_PER_TAP) && it + 1 < nit) {
+    if (it + 1 < nit) load_a((it + 1) / TAPS, (it + 1) % TAPS);
+    if (!MFPA_EXP_FLAG(a.dbg, 8)) compute(0, Bs0 + (it & 1) * (BN * LDK));
+    if (it + 1 < nit) {
       if (!MFPA_EXP_FLAG(a.dbg, 2)) __syncthreads();            // every wave is done reading As
       store_a((it + 1) / TAPS, As);
     }
@@ -644,134 +564,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
     if (tap == 2 && !MFPA_EXP_FLAG(a.dbg, 16)) store_a(chunk_n, As + ((chunk + 1) & 1) * (HPS * LDK));
   };
 
-  // ---- BDIR: weights straight from L1 / L2 into the operand registers (see the template's header comment) -------------------
-  struct AFrags { bf16x8 ah[MT], al[MT]; };
-  AFrags fa0, fa1;
-  bf16x8 bq[3][2][2];                                  // [ring slot = tap % 3][substep][hi, lo]
-  const int wn_s = __builtin_amdgcn_readfirstlane(wn);
-  auto load_bq = [&](int chunk, int tap, auto SLOT) __attribute__((always_inline)) {
-    constexpr int slot = decltype(SLOT)::value;
-    // 4 KB per (tap, chunk, 32-channel column tile): [substep][hi | lo][lane][16 B]
-    const char* wb = reinterpret_cast<const char*>(a.w) + ((((size_t)tap * nchunks + chunk) * (size_t)(a.Cout / 32) + (size_t)(n0 / 32 + wn_s)) << 12) + lane * 16;
-    bq[slot][0][0] = *reinterpret_cast<const bf16x8*>(wb);
-    bq[slot][0][1] = *reinterpret_cast<const bf16x8*>(wb + 1024);
-    bq[slot][1][0] = *reinterpret_cast<const bf16x8*>(wb + 2048);
-    bq[slot][1][1] = *reinterpret_cast<const bf16x8*>(wb + 3072);
-  };
-  auto read_afrags = [&](AFrags& f, const float* Asb, int tap_off, int sub) __attribute__((always_inline)) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-      f.al[mt] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(Asb + a_base[mt] + tap_off) + 32 * sub + 64);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-      f.ah[mt] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(Asb + a_base[mt] + tap_off) + 32 * sub);
-  };
-  auto mfma_d = [&](const AFrags& f, const bf16x8 bh, const bf16x8 bl) __attribute__((always_inline)) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.al[mt], bh, acc[mt][0], 0, 0, 0);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[mt], bl, acc[mt][0], 0, 0, 0);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[mt], bh, acc[mt][0], 0, 0, 0);
-  };
-  // one halo staging slot of chunk `chunk`: zero padding, the on-load affine + ReLU + dropout of the training forward, bf16 hi / lo
-  // split, two 8-byte LDS stores (store_a for a single slot)
-  auto split_slot = [&](auto IT, int chunk, float* Asn) __attribute__((always_inline)) {
-    constexpr int it = decltype(IT)::value;
-    const int pix = tid / (KC / 4) + it * (THREADS / (KC / 4));
-    const int c0 = chunk * KC;
-    const bool inside = (c0 < a.C0) ? (apix[it] >= 0) : src1_inside(apix[it]);
-    f32x4 v = areg[it];
-    if (!inside) v = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (a.in_scale0 != nullptr && c0 < a.C0 && inside) {           // training: the producer's BatchNorm + ReLU (+ dropout) on load; padding stays 0
-      const f32x4 sc = *reinterpret_cast<const f32x4*>(a.in_scale0 + c0 + 4 * aq);
-      const f32x4 sh = *reinterpret_cast<const f32x4*>(a.in_shift0 + c0 + 4 * aq);
-      v = v * sc + sh;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
-      if (a.drop_thresh) {
-        const int gy = (apix[it] >> 16) & 0x7fff, gx = apix[it] & 0xffff;
-        const unsigned long long e0 = (((unsigned long long)b * a.H + gy) * a.W + gx) * a.C0 + c0 + 4 * aq;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = mfpa_keep(a.drop_seed, a.drop_thresh, e0 + k) ? v[k] * a.drop_scale : 0.f;
-      }
-    }
-    bf16x4 hi, lo;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      hi[k] = (__bf16)v[k];
-      lo[k] = (__bf16)(v[k] - (float)hi[k]);
-    }
-    char* row = reinterpret_cast<char*>(Asn + pix * LDK);
-    *reinterpret_cast<bf16x4*>(row + 8 * aq) = hi;
-    *reinterpret_cast<bf16x4*>(row + 64 + 8 * aq) = lo;
-  };
-  // One tap: phase A = read A frags(it, s=1) || MFMA(s=0), request the weights of tile it+2 (slot (tap+2) % 3, whose tile it-1 was
-  // consumed by the previous phase B); phase B = read A frags(it+1, s=0) || MFMA(s=1).  The chunk's ONE barrier sits between the
-  // phases of tap 8: before it every wave has read the last fragments of this chunk's halo stage (rewritten at tap 2 of the next
-  // chunk), behind it the next chunk's stage -- split at tap 2 of this chunk by every wave -- is complete.
-  auto tap_body_d = [&](auto TAP, int chunk) __attribute__((always_inline)) {
-    constexpr int tap = decltype(TAP)::value;
-    constexpr int ntap = (tap + 1) % TAPS;
-    constexpr int tap_off = ((tap / 3) * HPW + (tap % 3)) * LDK, ntap_off = ((ntap / 3) * HPW + (ntap % 3)) * LDK;
-    constexpr int N_AR = 2 * MT, N_M = 3 * MT;
-    const int chunk_n = chunk + 1 < nchunks ? chunk + 1 : chunk;
-    const float* Asb = As + (chunk & 1) * (HPS * LDK);
-    const float* Asn = (tap == TAPS - 1) ? As + ((chunk + 1) & 1) * (HPS * LDK) : Asb;
-    read_afrags(fa1, Asb, tap_off, 1);
-    mfma_d(fa0, bq[tap % 3][0][0], bq[tap % 3][0][1]);
-    {
-      constexpr int t2 = (tap + 2) % TAPS;
-      load_bq((tap + 2 >= TAPS) ? chunk_n : chunk, t2, std::integral_constant<int, (tap + 2) % 3>{});
-    }
-    // pinned interleave: one fragment read behind each of the first MFMAs, the four weight loads behind the next, the rest bare
-    pin_reads<N_M - 1, N_AR>();
-    constexpr int used_a = pin_read_slots(N_M - 1, N_AR);
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);
-    if constexpr (N_M - used_a - 1 > 0) __builtin_amdgcn_sched_group_barrier(0x008, N_M - used_a - 1, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (tap == TAPS - 1) {
-      __syncthreads();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (tap == 0) load_a(chunk_n, 0);
-    read_afrags(fa0, Asn, ntap_off, 0);
-    mfma_d(fa1, bq[tap % 3][1][0], bq[tap % 3][1][1]);
-#if MFPA_BDIR_SPREAD_SPLIT
-    // The next chunk's halo (requested at tap 0) is split and stored ONE staging slot per tap, taps 2 .. 2 + A_F4 - 1, inside this
-    // phase's scheduling region: its ~20 vector instructions and two LDS stores ride in the MFMA gaps instead of forming a block
-    // of vector work that both waves of a SIMD reach together (they run the same program almost in lockstep) with the matrix
-    // pipe idle.  All of it lies before tap 8's barrier.
-    static_assert(A_F4 <= TAPS - 3, "one halo staging slot per tap, taps 2 .. 7");
-    if constexpr (tap >= 2 && tap - 2 < A_F4) {
-      split_slot(std::integral_constant<int, tap - 2>{}, chunk_n, As + ((chunk + 1) & 1) * (HPS * LDK));
-      // MFMA, fragment read, two vector instructions ... then the stores behind two more MFMAs
-#pragma unroll
-      for (int i = 0; i < N_AR; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-      __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-      __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-      if constexpr (N_M - N_AR - 2 > 0) __builtin_amdgcn_sched_group_barrier(0x008, N_M - N_AR - 2, 0);
-    } else
-#endif
-    {
-      pin_reads<N_M, N_AR>();
-      if constexpr (N_M - pin_read_slots(N_M, N_AR) > 0) __builtin_amdgcn_sched_group_barrier(0x008, N_M - pin_read_slots(N_M, N_AR), 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#if !MFPA_BDIR_SPREAD_SPLIT
-    if (tap == 2) store_a(chunk_n, As + ((chunk + 1) & 1) * (HPS * LDK));
-#endif
-  };
-
   if (C1SRC) {
     const double den = a.c1_denom ? a.c1_denom[b] : 1.0;
     for (int i = tid; i < SH * SW; i += THREADS) {
@@ -788,25 +580,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
   }
   MFPA_STAMP(1);                                       // C1SRC: the spectrogram patch and the first layer's weights are staged
   load_a(0, 0);
-  if constexpr (BDIR) {
-    load_bq(0, 0, Set0{});
-    load_bq(0, 1, Set1{});
-    store_a(0, As);
-    __syncthreads();
-    MFPA_STAMP(2);
-    read_afrags(fa0, As, 0, 0);
-    for (int chunk = 0; chunk < nchunks; ++chunk) {
-      tap_body_d(std::integral_constant<int, 0>{}, chunk);
-      tap_body_d(std::integral_constant<int, 1>{}, chunk);
-      tap_body_d(std::integral_constant<int, 2>{}, chunk);
-      tap_body_d(std::integral_constant<int, 3>{}, chunk);
-      tap_body_d(std::integral_constant<int, 4>{}, chunk);
-      tap_body_d(std::integral_constant<int, 5>{}, chunk);
-      tap_body_d(std::integral_constant<int, 6>{}, chunk);
-      tap_body_d(std::integral_constant<int, 7>{}, chunk);
-      tap_body_d(std::integral_constant<int, 8>{}, chunk);
-    }
-  } else if constexpr (PIPE) {
+  if constexpr (PIPE) {
     using Set2 = std::integral_constant<int, 2>;
     load_b_ct(0, 0, Set0{});
     store_a(0, As);
@@ -833,7 +607,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
     if (nit > 1) load_b(1, Set0{});
     __syncthreads();
     MFPA_STAMP(2);                                     // first halo tile (C1SRC: the first layer on it) and weight tile in LDS
-    if constexpr (MODE == 0 && MFPA_CONV_STATIC_TAPS != 0) {
+    if constexpr (MODE == 0) {
       // nine is odd: the parity of a chunk's first iteration alternates from chunk to chunk
       int chunk = 0;
       for (; chunk + 1 < nchunks; chunk += 2) {
@@ -865,62 +639,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
         acc[mt][nt][r] = v;
       }
   }
-  // 64-channel tiles of the plain loop (the full-resolution layers: 64 KB of output + 16 KB of pooled output per workgroup): the tile goes
-  // through LDS -- free once every wave has left the main loop -- and out as 16-byte pieces, a pixel's 64 channels by 16 adjacent lanes:
-  // 16 dwordx4 stores per thread instead of 64 scalar ones (the in-kernel timeline put the epilogue at 7.8 us of a 34-56 us workgroup
-  // lifetime), and the 2x2 max-pool reads its windows from the same tile.
-  constexpr bool LDS_EPI = MFPA_CONV_LDS_EPI && (MODE == 0 && !PIPE && BN == 64 && BM == 256 && PW == 32);
-  if constexpr (LDS_EPI) {
-    if (a.y != nullptr || a.y_pool != nullptr) {
-      float* T = reinterpret_cast<float*>(smem);                       // [BM][BN]
-      __syncthreads();
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = wm * WPX + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) T[m * BN + wn * (NT * 32) + nt * 32 + li] = acc[mt][nt][r];
-        }
-      __syncthreads();
-      constexpr int Q = BN / 4;                                        // 16-byte pieces per pixel
-      if (a.y != nullptr && !MFPA_EXP_FLAG(a.dbg, 4)) {
-        char* yb = reinterpret_cast<char*>(a.y + (size_t)b * a.yH * a.yW * a.Cout);
-#pragma unroll
-        for (int it = 0; it < BM * Q / THREADS; ++it) {
-          const int idx = tid + it * THREADS, p = idx / Q, q = idx % Q;
-          const int gy = y0 + p / PW, gx = x0p + p % PW;
-          if (gy < a.yH && gx < a.yW)
-            *reinterpret_cast<f32x4*>(yb + (((unsigned)gy * (unsigned)a.yW + (unsigned)gx) * (unsigned)a.Cout + (unsigned)(n0 + 4 * q)) * 4u) =
-                *reinterpret_cast<const f32x4*>(T + p * BN + 4 * q);
-        }
-      }
-      if (a.y_pool != nullptr) {
-        const int Ho = a.H / 2, Wo = a.W / 2;
-#pragma unroll
-        for (int it = 0; it < (BM / 4) * Q / THREADS; ++it) {
-          const int idx = tid + it * THREADS, pp = idx / Q, q = idx % Q;
-          const int ly = pp / (PW / 2), lx = pp % (PW / 2);
-          const int py = y0 / 2 + ly, px = x0p / 2 + lx;
-          if (py < Ho && px < Wo) {
-            const float* t0 = T + ((2 * ly) * PW + 2 * lx) * BN + 4 * q;
-            const f32x4 v00 = *reinterpret_cast<const f32x4*>(t0), v01 = *reinterpret_cast<const f32x4*>(t0 + BN);
-            const f32x4 v10 = *reinterpret_cast<const f32x4*>(t0 + PW * BN), v11 = *reinterpret_cast<const f32x4*>(t0 + PW * BN + BN);
-            f32x4 o;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = fmaxf(fmaxf(v00[k], v01[k]), fmaxf(v10[k], v11[k]));
-            *reinterpret_cast<f32x4*>(a.y_pool + (((size_t)b * Ho + py) * Wo + px) * a.Cout + n0 + 4 * q) = o;
-          }
-        }
-      }
-    }
-  }
-  if (!LDS_EPI && a.y != nullptr) {
+  if (a.y != nullptr) {
     // 32-bit byte offsets from a scalar per-clip base (the host checks that one clip's output fits 4 GB), the pixel offset
     // computed once for all of a lane's channels, and no bounds checks on interior tiles: the first form of this loop (64-bit
     // index arithmetic and an exec-mask branch per element) was up to 13 % of the 64-channel layers
-    const unsigned oW = (MODE == 1) ? 2u * (unsigned)a.W : (unsigned)a.yW;
-    const unsigned oH = (MODE == 1) ? 2u * (unsigned)a.H : (unsigned)a.yH;
+    const unsigned oW = (unsigned)a.yW, oH = (unsigned)a.yH;
     char* yb = reinterpret_cast<char*>(a.y + (size_t)b * oH * oW * a.Cout);
     const unsigned cout = (unsigned)a.Cout;
     const unsigned nb = (unsigned)(n0 + wn * (NT * 32) + li) * 4u;
@@ -932,9 +655,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
         const int m = wm * WPX + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         const int gy = y0 + m / PW, gx = x0p + m % PW;
         if (interior || (gy < a.yH && gx < a.yW)) {
-          unsigned pix;
-          if (MODE != 1) pix = (unsigned)gy * oW + (unsigned)gx;
-          else pix = (unsigned)(2 * gy + (ct_tap >> 1)) * oW + (unsigned)(2 * gx + (ct_tap & 1));
+          const unsigned pix = (unsigned)gy * oW + (unsigned)gx;
           char* yp = yb + (pix * cout * 4u + nb);
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt)
@@ -943,7 +664,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
       }
     }
   }
-  if (!LDS_EPI && MODE == 0 && a.y_pool != nullptr) {
+  if (MODE == 0 && a.y_pool != nullptr) {
     // MaxPool2d(2) (floor): every 2x2 window lives in ONE lane's accumulators (the two rows of a window are the
     // wave's two 32-pixel MFMA tiles for 32-wide patches, registers r / r+8 for 16-wide ones; the two columns are
     // registers r / r+1), so pooling needs no cross-lane traffic.
@@ -1015,14 +736,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 || conv_is_pipe(BN, PH,
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Weights-direct 3x3 convolution on v_mfma_f32_16x16x32_bf16 ("WD16", mfpa_conv_desc.w_layout 2).  Same structure as the BDIR form of
-// conv_mfma_kernel -- 8 waves = 2 pixel halves x 4 column tiles, a wave owns 128 pixels x 32 channels, the weight operand straight from
-// L1 / L2 out of a fragment-ordered image two taps ahead through a ring of three register sets, the halo tile double-buffered in LDS,
-// ONE barrier per 32-channel chunk, the next chunk's halo split one staging slot per tap inside the MFMA phases -- but the matrix
-// instruction is the 16 x 16 x 32 one: a whole 32-channel chunk is ONE k-step, and a quarter of the accumulator rows per instruction.
-// The weights-direct loop is clock (power) limited, and under the same loop with the same operand traffic the chip holds a higher clock
-// on this shape: a timing experiment with the 32 x 32 x 16 instructions of the BDIR kernel replaced one for two (wrong results) ran the
-// eleven >= 128-channel layers in 11.07-11.10 ms instead of 11.93-12.00 ms (64 clips), which is what this kernel is built on.
+// Weights-direct 3x3 convolution on v_mfma_f32_16x16x32_bf16 ("WD16", mfpa_conv_desc.w_layout 2): 8 waves = 2 pixel halves x 4 column
+// tiles, a wave owns 128 pixels x 32 channels, the weight operand comes straight from L1 / L2 out of a fragment-ordered image two taps
+// ahead through a ring of three register sets (no weight tile in LDS, no weight barrier), the halo tile is double-buffered in LDS with
+// ONE barrier per 32-channel chunk, and the next chunk's halo is split one staging slot per tap inside the MFMA phases.  A whole
+// 32-channel chunk is ONE k-step of the 16 x 16 x 32 instruction.  The weights-direct loop is clock (power) limited, and the chip holds
+// a higher clock on this instruction than on v_mfma_f32_32x32x16_bf16 under the same loop and operand traffic: 11.07-11.10 ms instead
+// of 11.93-12.00 ms for the eleven >= 128-channel layers (64 clips), which is what this kernel is built on.
 //   roles: A operand = weights (16 output channels x 32 k), B operand = pixels (32 k x 16 pixels), so D[channel][pixel]: a lane holds FOUR
 //          CONSECUTIVE CHANNELS of one pixel -- the epilogue stores 16-byte pieces (16 stores per wave instead of 64 scalar ones) and the
 //          2 x 2 max-pool needs one DPP swap of adjacent lanes;
@@ -1078,8 +798,8 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
   // PERSIST (WMW = 4): a workgroup walks tiles blockIdx.x, blockIdx.x + gridDim.x, ...; the halo of the next tile's first chunk is
   // requested and split under the last chunk of the current one, so a tile's prologue (a global round trip) and most of its epilogue
   // disappear behind the neighbours' MFMAs -- with 2 .. 4 chunks per tile they were a third of a workgroup's life.
-  constexpr bool PERSIST = (WMW == 4) || (MFPA_WD16_PERSIST2 != 0 && !ROWS && !SIDE && !PLAIN) || (MFPA_WD16_PERSIST_ROWS != 0 && ROWS && !SIDE && !PLAIN) ||
-                           (MFPA_WD16_PERSIST_PLAIN != 0 && PLAIN);
+  // The plain-bf16 (training) instantiations persist too: their MFMA time is a third, so prologue / epilogue weigh three times more.
+  constexpr bool PERSIST = (WMW == 4) || (!ROWS && !SIDE) || PLAIN;
   const int n0 = blockIdx.y * BN;
   const int Cin = a.C0 + a.C1;
   const int nchunks = Cin / KC;
@@ -1196,16 +916,6 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
     const unsigned* ao = aoffs0 + (chunk * KC < a.C0 ? 0 : A_F4 * THREADS) + tid;
 #pragma unroll
     for (int it = 0; it < A_F4; ++it) areg[it % AREGS][0] = __uint_as_float(ao[it * THREADS]);
-  };
-  // one staging slot of load_a_pre (MFPA_HALO_SPREAD: slot k is requested at tap k instead of all six at tap 0)
-  auto load_a_one = [&](auto IT, int chunk) __attribute__((always_inline)) {
-    constexpr int it = decltype(IT)::value;
-    if (MFPA_EXP_FLAG(a.dbg, 64)) return;
-    const int c0 = chunk * KC;
-    const bool from0 = c0 < a.C0;
-    const auto rs = clip_rsrc(from0 ? a.x0 : a.x1, S.b, from0 ? clip0 : clip1);
-    const unsigned toff = from0 ? S.t0 + (unsigned)c0 * (unsigned)ESZ : S.t1 + (unsigned)(c0 - a.C0) * (unsigned)ESZ;
-    areg[it % AREGS] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(__float_as_uint(areg[it % AREGS][0]) + toff), 0, 0));
   };
   auto load_a_pre = [&](int chunk) __attribute__((always_inline)) {
     if (MFPA_EXP_FLAG(a.dbg, 64)) return;
@@ -1366,7 +1076,8 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
   constexpr int N_W = PLAIN ? 2 : 4;                                   // weight-fragment loads of one tap
   // One tap.  Phase A: MFMA(pixel tiles 0..3 of tap t) || read tiles 4..7 of tap t, request the weights of tap t + 2.  Phase B: MFMA(tiles
   // 4..7) || read tiles 0..3 of tap t + 1, (tap 0) request the next chunk's halo, (taps 2..7) split one staging slot of it.  The chunk's
-  // one barrier sits between the phases of tap 8 (see BDIR).
+  // one barrier sits between the phases of tap 8: before it every wave has read the last fragments of this chunk's halo stage (rewritten
+  // from tap 2 of the next chunk on), behind it the next chunk's stage -- split at taps 2..7 of this chunk by every wave -- is complete.
   auto tap_body = [&](auto TAP, int chunk) __attribute__((always_inline)) {
     constexpr int tap = decltype(TAP)::value;
     constexpr int ntap = (tap + 1) % TAPS;
@@ -1430,11 +1141,7 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
       __builtin_amdgcn_sched_barrier(0);
       stamp(9);
     }
-#if MFPA_HALO_SPREAD
-    if constexpr (tap < A_F4) load_a_one(std::integral_constant<int, tap < A_F4 ? tap : 0>{}, chunk_n);
-#else
     if (tap == 0) load_a_pre(chunk_n);
-#endif
     // what the next tap 0 requests: chunk + 2; from the tile's last-but-one chunk on, the next tile's chunk 0, then its chunk 1
     if (tap == TAPS - 1) preload_offsets(chunk + 2 < nchunks ? chunk + 2 : chunk + 1 < nchunks ? 0 : 1 < nchunks ? 1 : 0);
     read_x(par ? fx0 : fx1, nxt, ntap_off, 0);
@@ -1650,13 +1357,8 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
   #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
       const int chl = wn * 32 + ct * 16 + 4 * g;                       // channel inside the workgroup's BN
-#if MFPA_EPI_LDS
       const f32x4 sc = *reinterpret_cast<const f32x4*>(epi + chl);
       const f32x4 sh = *reinterpret_cast<const f32x4*>(epi + BN + chl);
-#else
-      const f32x4 sc = a.scale ? *reinterpret_cast<const f32x4*>(a.scale + n0 + chl) : f32x4{1.f, 1.f, 1.f, 1.f};
-      const f32x4 sh = a.shift ? *reinterpret_cast<const f32x4*>(a.shift + n0 + chl) : f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
   #pragma unroll
       for (int pt = 0; pt < PT; ++pt)
   #pragma unroll
@@ -1797,13 +1499,8 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
         // the four channel groups of a wave through two ds_bpermute butterflies, the two channel-tile waves through LDS; then one
         // pixel per thread, stored coalesced
         float* red = reinterpret_cast<float*>(smem + 2 * STAGE + TBL * sizeof(unsigned)) + (a.in_scale0 ? 2 * a.C0 : 0);   // [2][256]
-#if MFPA_EPI_LDS
         const f32x4 w0 = *reinterpret_cast<const f32x4*>(epi + 2 * BN + wn * 32 + 4 * g);
         const f32x4 w1 = *reinterpret_cast<const f32x4*>(epi + 2 * BN + wn * 32 + 16 + 4 * g);
-#else
-        const f32x4 w0 = *reinterpret_cast<const f32x4*>(a.w1x1 + wn * 32 + 4 * g);
-        const f32x4 w1 = *reinterpret_cast<const f32x4*>(a.w1x1 + wn * 32 + 16 + 4 * g);
-#endif
   #pragma unroll
         for (int pt = 0; pt < PT; ++pt) {
           float v = 0.f;
@@ -1907,7 +1604,7 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
       mfpa_conv_stamps[0] = stamp_n;
     }
 #endif
-  } else if constexpr (PERSIST) {                                    // WMW = 2, tap-by-tap, persistent (MFPA_WD16_PERSIST2)
+  } else if constexpr (PERSIST) {                                    // WMW = 2, tap-by-tap, persistent
     read_x(fx0, smem, 0, 0);
     for (;;) {
       const int tile_n = tile + (int)gridDim.x;
@@ -1950,22 +1647,11 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
   }
 }
 
-#ifndef MFPA_CONV_WS64
-#define MFPA_CONV_WS64 1             // 64-channel inference launches on conv_ws64_kernel (csrc/unet_ws.hip); 0: conv_wd16_kernel<.., WMW = 4> (A/B builds)
-#endif
-#ifndef MFPA_CONV_WS_C1
-#define MFPA_CONV_WS_C1 1            // the UNet's first two layers (1 -> 64 computed in the loader waves on the matrix cores, 64 -> 64) on conv_ws64_kernel<C1SRC>
-#endif
-#ifndef MFPA_CONV_WS_ALL
-#define MFPA_CONV_WS_ALL 128         // conv_ws64_kernel also for outputs of 128 channels and more with at most this many input channels (0 = never): per layer,
-                                     // 64 clips: 64 -> 128 @ 128 x 125 431 -> 380 us, 128 -> 128 725 -> 704, 128 -> 256 @ 64 x 62 360 -> 345; from 256 input channels on it loses
-#endif
-#ifndef MFPA_CONV_WD16_64
-#define MFPA_CONV_WD16_64 64         // conv_wd16_kernel<.., WMW = 4> for 64-channel layers with at least this many input channels (no fused first layer / OutConv); 0 = off
-#endif
-#ifndef MFPA_CONV_WD16_ROWS
-#define MFPA_CONV_WD16_ROWS 512
-#endif
+// conv_wd16_kernel's ROWS loop form from this many input channels up: same-call pairs on the UNet's layers, 64 clips: +2 .. +4 % at 512 /
+// 1024 input channels, -1 .. -4 % at 64 .. 256 (its longer pipeline fill costs more than the halved fragment reads return when a tile has
+// only 2 .. 8 chunks)
+constexpr int CONV_WD16_ROWS = 512;
+
 template <int PH, int PW, int WMW = 2>
 int launch_wd16(ConvArgs& a, hipStream_t s) {
   a.tiles_x = (a.W + PW - 1) / PW;
@@ -1988,24 +1674,14 @@ int launch_wd16(ConvArgs& a, hipStream_t s) {
   a.dbg_lds_stamps = (int)lds;
   const_cast<size_t&>(lds) += 4096;
 #endif
-  static const int persist_env = MFPA_EXP_ENV("MFPA_CONV_WD16_PERSIST", 1);      // experiments: 0 = one workgroup per tile
-  const bool side_ = a.x0_bf16 || a.x1_bf16 || a.y_bf16 || a.stats_part;
-  const int cin_ = a.C0 + a.C1;
-  const bool rows_ = WMW == 2 && MFPA_CONV_WD16_ROWS > 0 && cin_ % 64 == 0 && cin_ >= MFPA_CONV_WD16_ROWS;
-  const bool persist2 = WMW == 2 && ((!side_ && !a.plain && ((MFPA_WD16_PERSIST2 != 0 && !rows_) || (MFPA_WD16_PERSIST_ROWS != 0 && rows_))) ||
-                                     (MFPA_WD16_PERSIST_PLAIN != 0 && a.plain));
-  if ((WMW == 4 && persist_env) || persist2) {                         // persistent: one workgroup per CU (and output-channel tile) walks the tiles
+  const int cin = a.C0 + a.C1;
+  const bool side = a.x0_bf16 || a.x1_bf16 || a.y_bf16 || a.stats_part;
+  const bool rows = WMW == 2 && cin % 64 == 0 && cin >= CONV_WD16_ROWS;
+  if (WMW == 4 || a.plain || (!side && !rows)) {                       // the kernel's PERSIST: one workgroup per CU (and output-channel tile) walks the tiles
     const int cus = mfpa_current_device_cus();
     const unsigned per = (unsigned)((cus > 0 ? cus : 256) / (int)grid.y);
     if (per >= 1 && grid.x > per) grid.x = per;
   }
-  // the ROWS loop form from 512 input channels up (MFPA_CONV_WD16_ROWS = that threshold; 0 = never): same-call pairs on the UNet's layers,
-  // 64 clips: +2 .. +4 % at 512 / 1024 input channels, -1 .. -4 % at 64 .. 256 (its longer pipeline fill costs more than the halved
-  // fragment reads return when a tile has only 2 .. 8 chunks)
-  static const int rows_min = MFPA_EXP_ENV("MFPA_CONV_WD16_ROWS", MFPA_CONV_WD16_ROWS);
-  const int cin = a.C0 + a.C1;
-  const bool side = a.x0_bf16 || a.x1_bf16 || a.y_bf16 || a.stats_part;
-  const bool rows = WMW == 2 && rows_min > 0 && cin % 64 == 0 && cin >= rows_min;
   if (a.in16) {                                                        // bf16 source: the plain-bf16 input-gradient convolutions
     if (!a.plain || a.x1_bf16 || cin % 64) return MFPA_EINVAL;         // (both sources bfloat16; source 1 IS its own bf16 copy)
     const bool fwd16 = a.in_scale0 != nullptr || a.x0_bf16 != nullptr || (a.y == nullptr && a.bz == nullptr);   // the training forward's form (AFF16)
@@ -2451,8 +2127,8 @@ __global__ __launch_bounds__(256) void conv1x1_out_kernel(const float* __restric
   }
 }
 
-template <int BN, int PH, int PW, int WM, int WN, int MODE, int PREC, bool C1SRC = false, int MT = 2, bool BDIR = false>
-int launch_conv(ConvArgs& a, int taps_y, hipStream_t s) {
+template <int BN, int PH, int PW, int WM, int WN, int MODE, int PREC, bool C1SRC = false>
+int launch_conv(ConvArgs& a, hipStream_t s) {
   constexpr int HALO = (MODE == 0) ? 1 : 0;
   constexpr int HP = (PW + 2 * HALO) * (PH + 2 * HALO);
   a.tiles_x = (a.W + PW - 1) / PW;
@@ -2460,111 +2136,71 @@ int launch_conv(ConvArgs& a, int taps_y, hipStream_t s) {
   static const int dbg_env = MFPA_EXP_ENV("MFPA_CONV_DBG", 0);
   a.dbg = dbg_env;
   if ((long long)a.tiles_x * a.tiles_y * a.B > 0x7fffffffLL) return MFPA_EINVAL;
-  constexpr bool ADB = BDIR || conv_is_pipe(BN, PH, PW, WM, WN, MODE, PREC, MT);    // PIPE of the kernel: two padded halo stages
+  constexpr bool PIPE = conv_is_pipe(WM, WN, MODE, PREC);           // the kernel's PIPE: two padded halo stages
   constexpr int THREADS = 64 * WM * WN;
-  constexpr int HPS = ADB ? ((HP * (KC / 4) + THREADS - 1) / THREADS) * (THREADS / (KC / 4)) : HP;
-  const size_t lds = sizeof(float) * ((size_t)(ADB ? 2 : 1) * HPS * LDK + (BDIR ? 0 : 2) * (size_t)BN * LDK + (C1SRC ? (PH + 4) * (PW + 4) + 9 * 64 : 0));
-  dim3 grid((unsigned)((long long)a.tiles_x * a.tiles_y * a.B), (unsigned)(taps_y * (a.Cout / BN)));
-  hipLaunchKernelGGL((conv_mfma_kernel<BN, PH, PW, WM, WN, MODE, PREC, C1SRC, MT, BDIR>), grid, dim3(64 * WM * WN), lds, s, a);
+  constexpr int HPS = PIPE ? ((HP * (KC / 4) + THREADS - 1) / THREADS) * (THREADS / (KC / 4)) : HP;
+  const size_t lds = sizeof(float) * ((size_t)(PIPE ? 2 : 1) * HPS * LDK + 2 * (size_t)BN * LDK + (C1SRC ? (PH + 4) * (PW + 4) + 9 * 64 : 0));
+  dim3 grid((unsigned)((long long)a.tiles_x * a.tiles_y * a.B), (unsigned)(a.Cout / BN));
+  hipLaunchKernelGGL((conv_mfma_kernel<BN, PH, PW, WM, WN, MODE, PREC, C1SRC>), grid, dim3(64 * WM * WN), lds, s, a);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
 }
 
+// 128-channel tiles of the plain loop: the 8-wave 256-pixel shape from this many input channels on (the bf16x3 3x3 convolution; the
+// others keep round 1's measured 256)
+constexpr int CONV_BIG_MIN_CIN = 64;
+// conv_ws64_kernel also takes outputs of 128 channels and more with at most this many input channels: per layer, 64 clips: 64 -> 128 @
+// 128 x 125 431 -> 380 us, 128 -> 128 725 -> 704, 128 -> 256 @ 64 x 62 360 -> 345; from 256 input channels on it loses
+constexpr int CONV_WS_ALL = 128;
+
 // Which bf16x3 weight image does the fastest kernel for this shape read?  2 = the fragment-ordered image of the 16 x 16 x 32
-// weights-direct kernel (conv_wd16_kernel: 3x3 convolution, 128-channel output tiles, >= 64 input channels, the 8 x 32 patches of the
-// wide levels or the 16 x 16 patches of the 16 x 15 level), 1 = the image of the 32 x 32 x 16 weights-direct form (BDIR; with
-// MFPA_CONV_WD16 = 0, and the 64-channel tiles with MFPA_CONV_BDIR64), 0 = the row image.
+// weights-direct kernels (conv_ws64_kernel, conv_wd16_kernel: 3x3 convolution, >= 64 input channels, the 8 x 32 patches of the wide
+// levels or the 16 x 16 patches of the 16 x 15 level), 0 = the row image.  The 64-channel outputs take it from 64 input channels on:
+// with its persistent tile loop conv_wd16_kernel<.., WMW = 4> beats the plain loop there (64 -> 64 @ 257 x 251, 64 clips, 1366 -> 1008 us).
 static int conv_weight_layout(int H, int W, int Cin, int Cout, int mode, int precision) {
-#ifdef MFPA_CONV_NO_BDIR
-  return 0;
-#endif
-  if (mode != 0 || precision != 1 || Cin < MFPA_CONV_BIG_MIN_CIN) return 0;
-  if (Cout % 128) {                                                    // 64-channel output tiles
-    static const int wd64 = MFPA_EXP_ENV("MFPA_CONV_WD16_64", MFPA_CONV_WD16_64);
-    // (wd64 = the smallest C_in that takes it.  Before its tile loop was persistent, two-chunk tiles ran better on the plain-loop
-    // kernel, whose two co-resident workgroups hide each other's prologue and epilogue; with the persistent loop: 64 -> 64 @ 257 x 251,
-    // 64 clips, 1366 -> 1008 us)
-    if (MFPA_CONV_WD16 && wd64 > 0 && Cin >= wd64 && Cout % 64 == 0 && Cin % 64 == 0 && W > 16 && H >= 8) return 2;
-    return (MFPA_CONV_BDIR64 && Cout % 64 == 0 && W > 16 && H >= 8) ? 1 : 0;
-  }
-  if (W > 16 && H >= 8) return MFPA_CONV_WD16 ? 2 : 1;
-  if (W <= 16 && H >= 16 && MFPA_CONV_BOTTLENECK8) return MFPA_CONV_WD16 ? 2 : 1;
-  return 0;
+  if (mode != 0 || precision != 1 || Cin < CONV_BIG_MIN_CIN) return 0;
+  const bool wide = W > 16 && H >= 8;
+  if (Cout % 128) return (wide && Cout % 64 == 0 && Cin % 64 == 0) ? 2 : 0;     // 64-channel output tiles
+  return (wide || (W <= 16 && H >= 16)) ? 2 : 0;
 }
 
 // Tile choice.  Waves always own 64 pixels x 64 channels.
+//   w_layout 2 (bf16x3 3x3 convolution): conv_ws64_kernel (csrc/unet_ws.hip: 4 compute waves of 128 px x 32 ch + 4 loader waves) for the
+//                    fused first layer, the 64-channel outputs and the wider ones up to CONV_WS_ALL input channels; conv_wd16_kernel
+//                    for the shapes it does not serve and for the training step's launches.
 //   Cout % 128 == 0: 128-channel tiles; 8 waves on 8x32-pixel patches (256 x 128: half the weight traffic and
 //                    barriers per MFMA) when K = 9*Cin is long enough to amortise the prologue/epilogue of a
 //                    one-workgroup-per-CU kernel, else 4 waves on 4x32 patches (two workgroups per CU overlap).
 //   otherwise      : 64-channel tiles, 4 waves stacked along M on 8x32 patches (256 x 64).
-//   W <= 16 (the 16x15 bottleneck): 8x16 patches.
+//   W <= 16 (the 16x15 bottleneck): 16x16 patches on 8 waves for the bf16x3 3x3 convolution's 128-channel tiles, else 8x16 patches.
 template <int MODE, int PREC>
 int dispatch_conv_p(ConvArgs& a, hipStream_t s) {
-  static const int ct_old = MFPA_EXP_ENV("MFPA_CONVT_OLD", 0);   // experiments: generic kernel
-  if (MODE == 1 && !ct_old) return a.W > 16 ? launch_convT<4, 32, PREC>(a, s) : launch_convT<8, 16, PREC>(a, s);
-  const int taps_y = (MODE == 1) ? 4 : 1;
+  static_assert(MODE == 0 || MODE == 2, "the transposed convolution (MODE 1) runs on launch_convT");
   const bool bn128 = (a.Cout % 128 == 0);
   if constexpr (MODE == 0 && PREC == 1) {
-    if (a.w_frag == 2) {   // the 16 x 16 x 32 weights-direct kernel and its image
+    if (a.w_frag) {        // w_layout 2: the 16 x 16 x 32 weights-direct kernels
       if (conv_weight_layout(a.H, a.W, a.C0 + a.C1, a.Cout, 0, 1) != 2 || (a.w1x1 && bn128)) return MFPA_EINVAL;
-      if (a.c1_x32 || a.c1_spec64) {      // fused first layer + fragment image: conv_ws64_kernel<C1SRC> only (mfpa_conv_c1_layout() says where)
-        return (MFPA_CONV_WS64 && MFPA_CONV_WS_C1 && mfpa_unet::conv_ws64_serves(a)) ? mfpa_unet::launch_conv_ws64(a, s) : MFPA_EINVAL;
-      }
-      if (!bn128) {
-        // round 5: the wave-specialised kernel (csrc/unet_ws.hip: 4 compute waves of 128 px x 32 ch + 4 loader waves) takes the inference launches
-        static const int ws64 = MFPA_EXP_ENV("MFPA_CONV_WS64", MFPA_CONV_WS64);
-        if (ws64 && mfpa_unet::conv_ws64_serves(a)) return mfpa_unet::launch_conv_ws64(a, s);
-        if (a.x0_split || a.x1_split || a.y_split || a.y_pool_split) return MFPA_EINVAL;   // (a run-time A/B switch sent a split-layout launch here: only conv_ws64_kernel knows that layout)
-        return launch_wd16<8, 32, 4>(a, s);                             // 64-channel output tiles: 4 x 2 waves of 64 px x 32 ch
-      }
-      {
-        // the same kernel for 128-channel-multiple outputs (two or more workgroup rows of 64 channels): per-layer A/B, see NOTES.md R5
-        static const int ws_all = MFPA_EXP_ENV("MFPA_CONV_WS_ALL", MFPA_CONV_WS_ALL);
-        const int cin_ = a.C0 + a.C1;
-        if (ws_all && cin_ <= ws_all && mfpa_unet::conv_ws64_serves(a)) return mfpa_unet::launch_conv_ws64(a, s);
-      }
-      if (a.x0_split || a.x1_split || a.y_split || a.y_pool_split) return MFPA_EINVAL;     // as above
-      if (a.W > 16) return launch_wd16<8, 32>(a, s);
-      return launch_wd16<16, 16>(a, s);
-    }
-    if (a.w_frag) {        // the caller packed the fragment-ordered image: only the BDIR kernels read it (conv_weight_layout() said so)
-      if (!conv_weight_layout(a.H, a.W, a.C0 + a.C1, a.Cout, 0, 1) || a.c1_x32 || a.c1_spec64) return MFPA_EINVAL;
-      if (!bn128) return launch_conv<64, 8, 32, 4, 2, 0, 1, false, 2, true>(a, 1, s);     // 64-channel layers: 8 waves of 64 px x 32 ch
-      if (a.W > 16) return launch_conv<128, 8, 32, 2, 4, 0, 1, false, 4, true>(a, 1, s);
-      return launch_conv<128, 16, 16, 2, 4, 0, 1, false, 4, true>(a, 1, s);
+      const bool c1 = a.c1_x32 || a.c1_spec64;
+      if ((c1 || !bn128 || a.C0 + a.C1 <= CONV_WS_ALL) && mfpa_unet::conv_ws64_serves(a)) return mfpa_unet::launch_conv_ws64(a, s);
+      if (c1 || a.x0_split || a.x1_split || a.y_split || a.y_pool_split) return MFPA_EINVAL;   // only conv_ws64_kernel knows these
+      if (!bn128) return launch_wd16<8, 32, 4>(a, s);                   // 64-channel output tiles: 4 x 2 waves of 64 px x 32 ch
+      return a.W > 16 ? launch_wd16<8, 32>(a, s) : launch_wd16<16, 16>(a, s);
     }
   }
-  static const int wm_env = MFPA_EXP_ENV("MFPA_CONV_WM", 0);   // experiments
-  const int cin = a.C0 + a.C1;
-  const bool big = (wm_env == 4) || (wm_env == 0 && cin >= ((PREC == 1 && MODE == 0) ? MFPA_CONV_BIG_MIN_CIN : 256));   // the plain loop keeps round 1's measured threshold
-  constexpr int WN64 = MFPA_CONV_WN64;   // 2: the pipelined 8-wave shape with waves of 64 px x 32 ch (measured 5-10 % slower than the 4-wave shape)
+  const bool big = a.C0 + a.C1 >= ((PREC == 1 && MODE == 0) ? CONV_BIG_MIN_CIN : 256);
   if (MODE == 0 && (a.c1_x32 || a.c1_spec64)) {        // checked by the caller: C0 == 64, C1 == 0, Cout == 64, W > 16, H >= 8
-    return launch_conv<64, 8, 32, 4, WN64, 0, PREC, true>(a, 1, s);
+    return launch_conv<64, 8, 32, 4, 1, 0, PREC, true>(a, s);
   }
   if (a.W > 16 && a.H >= 8) {
-    if (!bn128) return launch_conv<64, 8, 32, 4, WN64, MODE, PREC>(a, taps_y, s);
-#if MFPA_CONV_MT4 || defined(MFPA_EXPERIMENTS)
-    if constexpr (MODE == 0 && PREC == 1) {
-      static const int mt4 = MFPA_EXP_ENV("MFPA_CONV_MT4", MFPA_CONV_MT4);
-      if (big && mt4) return launch_conv<128, 8, 32, 2, 2, MODE, PREC, false, 4>(a, taps_y, s);
-    }
-#endif
-    if (big) return launch_conv<128, 8, 32, 4, 2, MODE, PREC>(a, taps_y, s);
-    return launch_conv<128, 4, 32, 2, 2, MODE, PREC>(a, taps_y, s);
+    if (!bn128) return launch_conv<64, 8, 32, 4, 1, MODE, PREC>(a, s);
+    if (big) return launch_conv<128, 8, 32, 4, 2, MODE, PREC>(a, s);
+    return launch_conv<128, 4, 32, 2, 2, MODE, PREC>(a, s);
   }
   if (a.W > 16) {
-    return bn128 ? launch_conv<128, 4, 32, 2, 2, MODE, PREC>(a, taps_y, s) : launch_conv<64, 4, 32, 2, 1, MODE, PREC>(a, taps_y, s);
+    return bn128 ? launch_conv<128, 4, 32, 2, 2, MODE, PREC>(a, s) : launch_conv<64, 4, 32, 2, 1, MODE, PREC>(a, s);
   }
-#if MFPA_CONV_BOTTLENECK8
-#if MFPA_CONV_MT4 || defined(MFPA_EXPERIMENTS)
-  if constexpr (MODE == 0 && PREC == 1) {
-    static const int mt4b = MFPA_EXP_ENV("MFPA_CONV_MT4", MFPA_CONV_MT4);
-    if (bn128 && a.H >= 16 && mt4b >= 2) return launch_conv<128, 16, 16, 2, 2, MODE, PREC, false, 4>(a, taps_y, s);
-  }
-#endif
-  if (bn128 && MODE == 0 && PREC == 1 && a.H >= 16) return launch_conv<128, 16, 16, 4, 2, MODE, PREC>(a, taps_y, s);
-#endif
-  return bn128 ? launch_conv<128, 8, 16, 2, 2, MODE, PREC>(a, taps_y, s) : launch_conv<64, 8, 16, 2, 1, MODE, PREC>(a, taps_y, s);
+  if (bn128 && MODE == 0 && PREC == 1 && a.H >= 16) return launch_conv<128, 16, 16, 4, 2, MODE, PREC>(a, s);
+  return bn128 ? launch_conv<128, 8, 16, 2, 2, MODE, PREC>(a, s) : launch_conv<64, 8, 16, 2, 1, MODE, PREC>(a, s);
 }
 
 template <int MODE>
@@ -2572,7 +2208,12 @@ int dispatch_conv(ConvArgs& a, hipStream_t s, int precision = 0) {
   // the halo loader packs pixel coordinates into 16 bits each and addresses one clip's input with 32-bit byte offsets
   if (a.H > 32767 || a.W > 32767) return MFPA_EINVAL;
   if ((MODE == 2 ? 4LL : 1LL) * a.H * a.W * a.C0 * 4 > 0xffffffffLL || 1LL * a.H1 * a.W1 * a.C1 * 4 > 0xffffffffLL) return MFPA_EINVAL;
-  return precision ? dispatch_conv_p<MODE, 1>(a, s) : dispatch_conv_p<MODE, 0>(a, s);
+  if constexpr (MODE == 1) {
+    if (precision) return a.W > 16 ? launch_convT<4, 32, 1>(a, s) : launch_convT<8, 16, 1>(a, s);
+    return a.W > 16 ? launch_convT<4, 32, 0>(a, s) : launch_convT<8, 16, 0>(a, s);
+  } else {
+    return precision ? dispatch_conv_p<MODE, 1>(a, s) : dispatch_conv_p<MODE, 0>(a, s);
+  }
 }
 
 }  // namespace
@@ -2640,7 +2281,7 @@ int mfpa_conv_mfma(const mfpa_conv_desc* d, void* stream) {
     a.c1_w = d->c1_w; a.c1_scale = d->c1_scale; a.c1_shift = d->c1_shift;
   }
   if (d->precision < 0 || d->precision > 2) return MFPA_EINVAL;
-  if (d->w_layout < 0 || d->w_layout > 2) return MFPA_EINVAL;
+  if (d->w_layout != 0 && d->w_layout != 2) return MFPA_EINVAL;         // the row image or the fragment image of the weights-direct kernels
   if (d->w_layout != 0 && (d->mode != 0 || d->precision < 1)) return MFPA_EINVAL;
   // plain bf16: conv_wd16_kernel (mode 0: it reads the hi halves of the fragment image), or -- round 6 -- the transposed convolution of the training
   // step and its input gradient (modes 1 / 2 on the row image: the hi halves of the staged operands)
@@ -2674,7 +2315,7 @@ int mfpa_conv_mfma(const mfpa_conv_desc* d, void* stream) {
   a.bz16 = (d->bwd_z != nullptr && d->bwd_z_is_bf16) ? 1 : 0;
   a.bz = d->bwd_z; a.bz_scale = d->bwd_scale; a.bz_shift = d->bwd_shift; a.bz_mean = d->bwd_mean; a.bz_invstd = d->bwd_invstd;
   if (any_split) {                                                       // only conv_ws64_kernel reads / writes the split layout
-    if (!(MFPA_CONV_WS64 && mfpa_unet::conv_ws64_serves(a)) || (a.Cout % 128 == 0 && !(MFPA_CONV_WS_ALL > 0 && d->C0 + d->C1 <= MFPA_CONV_WS_ALL))) return MFPA_EINVAL;
+    if (!mfpa_unet::conv_ws64_serves(a) || (a.Cout % 128 == 0 && d->C0 + d->C1 > CONV_WS_ALL)) return MFPA_EINVAL;
   }
   hipStream_t s = mfpa_stream(stream);
   const int prec = d->precision ? 1 : 0;                                 // kernel family: fp32 MFMA or the bf16 matrix cores
@@ -2692,15 +2333,15 @@ int mfpa_exp_conv_stamps(unsigned long long* buf) {       // experiments build o
 int mfpa_conv_c1_layout(int H, int W) {
   if (H < 1 || W < 1) return MFPA_EINVAL;
   // the fused first-layer launch (mfpa_conv_desc.c1_*, 64 -> 64) reads the fragment image 2 exactly where conv_ws64_kernel<C1SRC> takes it
-  return (MFPA_CONV_WS64 && MFPA_CONV_WS_C1 && conv_weight_layout(H, W, 64, 64, 0, 1) == 2 && W > 16 && H >= 8) ? 2 : 0;
+  return (conv_weight_layout(H, W, 64, 64, 0, 1) == 2 && W > 16 && H >= 8) ? 2 : 0;
 }
 
 int mfpa_conv_scale_folds(int H, int W, int Cin, int Cout) {
   if (H < 1 || W < 1 || Cin < 1 || Cout < 1) return MFPA_EINVAL;
   if (conv_weight_layout(H, W, Cin, Cout, 0, 1) != 2 || Cout % 64 || Cin % KC || W <= 16 || H < 8) return 0;
-  // the dispatcher's own routing (dispatch_conv_p): 64-channel-multiple outputs that are not 128-multiples always, the others up to MFPA_CONV_WS_ALL input channels
-  if (Cout % 128) return MFPA_CONV_WS64 ? 1 : 0;
-  return (MFPA_CONV_WS_ALL > 0 && Cin <= MFPA_CONV_WS_ALL) ? 1 : 0;
+  // the dispatcher's own routing (dispatch_conv_p): 64-channel-multiple outputs that are not 128-multiples always, the others up to CONV_WS_ALL input channels
+  if (Cout % 128) return 1;
+  return Cin <= CONV_WS_ALL ? 1 : 0;
 }
 
 int mfpa_conv_weight_layout(int H, int W, int Cin, int Cout, int mode, int precision) {

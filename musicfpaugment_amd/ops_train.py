@@ -57,8 +57,11 @@ DEVICE_PACK = True    # operand images of the weights built by mfpa_pack_conv_we
 def pack_weights(w: torch.Tensor, precision: int, flip_transpose: bool = False, row0: int = 0, nrows: Optional[int] = None,
                  layout: int = 0):
     """Master weights [taps][Co][Ci] -> the operand image of one conv launch (see mfpa_pack_conv_weights): forward operand, or with
-    flip_transpose the input-gradient operand [taps][ci in row0..row0+nrows][Co] (3x3 kernels flipped).  `layout` 1 (precision 1
-    only): the fragment-ordered image of the weights-direct kernels (mfpa_conv_desc.w_layout)."""
+    flip_transpose the input-gradient operand [taps][ci in row0..row0+nrows][Co] (3x3 kernels flipped).  `layout` 2 (precision 1
+    only): the fragment-ordered image of the weights-direct kernels (mfpa_conv_desc.w_layout); any other non-zero layout raises
+    ValueError."""
+    if layout not in (0, 2):
+        raise ValueError(f"no weight image in layout {layout}")
     taps, Co, Ci = w.shape
     if nrows is None:
         nrows = (Ci if flip_transpose else Co) - row0
@@ -157,8 +160,8 @@ _PACK_CACHE: Optional[PackCache] = None      # set by UNetTrainEngine around its
 
 
 def weight_layout(H: int, W: int, cin: int, cout: int, precision: int, mode: int = 0) -> int:
-    """Which bf16x3 image the fastest kernel for this convolution reads (mfpa_conv_weight_layout): 0 = the row image, 1 / 2 = the
-    fragment-ordered images of the weights-direct kernels."""
+    """Which bf16x3 image the fastest kernel for this convolution reads (mfpa_conv_weight_layout): 0 = the row image, 2 = the
+    fragment-ordered image of the weights-direct kernels."""
     if precision < 1 or mode != 0 or not K.USE_WEIGHTS_DIRECT:
         return 0
     return int(lib().mfpa_conv_weight_layout(H, W, cin, cout, 0, 1))

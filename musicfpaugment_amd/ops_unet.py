@@ -56,32 +56,23 @@ def split_bf16x3(w: torch.Tensor) -> torch.Tensor:
 
 def frag_layout() -> int:
     """Which fragment-ordered image the library's weights-direct kernels read (mfpa_conv_weight_layout on a representative shape):
-    2 = the 16 x 16 x 32 form (conv_wd16_kernel), 1 = the 32 x 32 x 16 form (BDIR), 0 = none."""
+    2 = the 16 x 16 x 32 form (conv_ws64_kernel, conv_wd16_kernel), 0 = none."""
     return int(lib().mfpa_conv_weight_layout(128, 125, 128, 128, 0, 1))
 
 
 def split_bf16x3_frag(w: torch.Tensor, layout: int = 2) -> torch.Tensor:
-    """Kernel-layout fp32 weights [taps][Cout][Cin] (Cout % 32 == 0, Cin % 32 == 0) -> a FRAGMENT-ORDERED bf16x3 image of the
-    "weights direct" convolution kernels (csrc/unet.hip; mfpa_conv_desc.w_layout = `layout`): a wave reads the MFMA weight operand of a
-    column tile as 1 KB contiguous pieces, one 16-byte fragment per lane.  Same split w = hi + lo as split_bf16x3.
-      layout 2 (v_mfma_f32_16x16x32_bf16, conv_wd16_kernel): [tap][chunk = Cin / 32][Cout / 16][hi | lo][lane 64][8 bf16], lane
-               (g = l >> 4, c = l & 15) = output channel 16 t + c, input channels 32 chunk + 8 g .. + 7;
-      layout 1 (v_mfma_f32_32x32x16_bf16, BDIR): [tap][chunk][Cout / 32][substep 2][hi | lo][lane 64][8 bf16], lane (lh = l >> 5,
-               li = l & 31) = output channel 32 n + li, input channels 32 chunk + 16 substep + 8 lh .. + 7.
-    Opaque float32 tensor of w's shape."""
+    """Kernel-layout fp32 weights [taps][Cout][Cin] (Cout % 16 == 0, Cin % 32 == 0) -> the FRAGMENT-ORDERED bf16x3 image of the
+    "weights direct" convolution kernels (mfpa_conv_desc.w_layout 2; v_mfma_f32_16x16x32_bf16 in conv_ws64_kernel / conv_wd16_kernel): a
+    wave reads the MFMA weight operand of a column tile as 1 KB contiguous pieces, one 16-byte fragment per lane.  Same split w = hi + lo
+    as split_bf16x3.  [tap][chunk = Cin / 32][Cout / 16][hi | lo][lane 64][8 bf16], lane (g = l >> 4, c = l & 15) = output channel
+    16 t + c, input channels 32 chunk + 8 g .. + 7.  Opaque float32 tensor of w's shape.  `layout` must be 2."""
+    if layout != 2:
+        raise ValueError(f"no fragment-ordered weight image in layout {layout} (only 2)")
     t, co, ci = w.shape
-    if layout == 2:
-        w6 = w.reshape(t, co // 16, 16, ci // 32, 4, 8)                            # [t][ct16][c][chunk][g][j]
-        hi = w6.to(torch.bfloat16)
-        lo = (w6 - hi.float()).to(torch.bfloat16)
-        img = torch.stack([hi, lo], dim=0).permute(1, 4, 2, 0, 5, 3, 6).contiguous()    # [t][chunk][ct16][hl][g][c][j]
-        return img.view(torch.float32).reshape(t, co, ci)
-    if layout != 1:
-        raise ValueError("layout must be 1 or 2")
-    w6 = w.reshape(t, co // 32, 32, ci // 32, 2, 2, 8)                             # [t][n32][li][chunk][s][lh][j]
+    w6 = w.reshape(t, co // 16, 16, ci // 32, 4, 8)                                # [t][ct16][c][chunk][g][j]
     hi = w6.to(torch.bfloat16)
     lo = (w6 - hi.float()).to(torch.bfloat16)
-    img = torch.stack([hi, lo], dim=0).permute(1, 4, 2, 5, 0, 6, 3, 7).contiguous()    # [t][chunk][n32][s][hl][lh][li][j]
+    img = torch.stack([hi, lo], dim=0).permute(1, 4, 2, 0, 5, 3, 6).contiguous()    # [t][chunk][ct16][hl][g][c][j]
     return img.view(torch.float32).reshape(t, co, ci)
 
 
@@ -98,7 +89,7 @@ class WeightImage(NamedTuple):
     """A weight operand as a kernel reads it: the tensor alone (opaque float32, the fp32 weights' shape) cannot say which image it is."""
     t: torch.Tensor
     precision: int               # 0 fp32 products, 1 bf16x3 (pre-split)
-    layout: int                  # 0 the row image [tap][Cout][Cin]; 1 / 2 a fragment image (mfpa_conv_desc.w_layout; precision 0: frag_f32)
+    layout: int                  # 0 the row image [tap][Cout][Cin]; 2 the fragment image (mfpa_conv_desc.w_layout; precision 0: frag_f32)
     scale_folded: bool = False   # the folded BatchNorm scale is multiplied in: the launch passes out_scale = None
 
 
@@ -106,7 +97,7 @@ def weight_image(w: torch.Tensor, precision: int, layout: int = 0, scale: Option
     """Kernel-layout fp32 weights [taps][Cout][Cin] (times `scale` (Cout) if given) -> their image; the fp32 row image is `w` itself."""
     if scale is not None:
         w = w * scale[None, :, None]
-    if layout != 0 and precision != 1 and (precision, layout) != (0, 2):
+    if layout not in (0, 2) or (layout and precision not in (0, 1)):
         raise ValueError(f"no weight image of precision {precision} in layout {layout}")
     t = (split_bf16x3(w) if precision == 1 else w) if layout == 0 else (split_bf16x3_frag(w, layout) if precision == 1 else frag_f32(w))
     return WeightImage(t, precision, layout, scale is not None)

@@ -73,6 +73,18 @@ def test_argument_errors_do_not_touch_the_gpu(lib):
     assert h.mfpa_conv_mfma(ctypes.byref(d), None) == lib.EINVAL                          # C0 % 32
     d = lib.ConvDesc(x0=1, w=1, y=1, C0=64, C1=0, B=0, H=8, W=8, Cout=64)
     assert h.mfpa_conv_mfma(ctypes.byref(d), None) == 0                                   # empty batch
+    for lay in (1, 3, -1):                                                                # w_layout is 0 or 2 (1 is not offered)
+        d = lib.ConvDesc(x0=1, w=1, y=1, C0=128, C1=0, B=1, H=128, W=125, Cout=128, mode=0, precision=1, w_layout=lay)
+        assert h.mfpa_conv_mfma(ctypes.byref(d), None) == lib.EINVAL
+    assert h.mfpa_pack_conv_weights(1, 9, 64, 64, 0, 0, 64, 2, 1, None) == lib.EINVAL      # packing code 2 (the w_layout-1 image)
+    assert h.mfpa_pack_conv_weights(1, 9, 64, 64, 1, 0, 64, 2, 1, None) == lib.EINVAL
+    # mfpa_conv_weight_layout answers 0 or 2 over the UNet's level sizes and channel counts, any mode / precision
+    for H, W in [(257, 251), (128, 125), (64, 62), (32, 31), (16, 15), (257, 249), (128, 124), (40, 70), (20, 35), (10, 17), (5, 8)]:
+        for cin in (32, 64, 128, 192, 256, 384, 512, 768, 1024):
+            for cout in (64, 128, 256, 512, 1024):
+                for mode, prec in [(0, 0), (0, 1), (0, 2), (1, 1), (2, 1)]:
+                    assert h.mfpa_conv_weight_layout(H, W, cin, cout, mode, prec) in (0, 2), (H, W, cin, cout, mode, prec)
+    assert h.mfpa_conv_weight_layout(128, 125, 128, 128, 0, 1) == 2
     g = lib.WgradDesc(dz=1, x0=1, dw=1, C0=96, C1=0, B=1, H=8, W=8, Cout=64)
     assert h.mfpa_wgrad_mfma(ctypes.byref(g), None) == lib.EINVAL                         # C0 % 64
     g = lib.WgradDesc(dz=1, x0=1, dw=1, C0=64, C1=0, B=1, H=8, W=8, Cout=64, precision=7)

@@ -694,12 +694,18 @@ def test_device_weight_pack_equals_the_host_packing():
                 want = T.pack_weights(w, prec, ft, row0, nrows)
                 T.DEVICE_PACK = True
                 assert got.shape == want.shape and torch.equal(got.view(torch.int32), want.view(torch.int32)), (taps, co, ci, prec, ft)
-                for lay in ((1, 2) if prec == 1 else ()):        # the fragment-ordered images of the weights-direct kernels (mfpa_conv_desc.w_layout)
+                for lay in ((2,) if prec == 1 else ()):          # the fragment-ordered image of the weights-direct kernels (mfpa_conv_desc.w_layout)
                     got = T.pack_weights(w, 1, ft, row0, nrows, layout=lay)
                     T.DEVICE_PACK = False
                     want = T.pack_weights(w, 1, ft, row0, nrows, layout=lay)
                     T.DEVICE_PACK = True
                     assert got.shape == want.shape and torch.equal(got.view(torch.int32), want.view(torch.int32)), (taps, co, ci, "frag", lay, ft)
+    # layout 1 (the 32 x 32 x 16 fragment order) is packed by neither path: refused before any launch
+    for device_pack in (True, False):
+        T.DEVICE_PACK = device_pack
+        with pytest.raises(ValueError):
+            T.pack_weights(w, 1, layout=1)
+    T.DEVICE_PACK = True
 
 
 def test_batched_weight_repack_equals_the_single_launches():

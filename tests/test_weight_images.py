@@ -21,12 +21,14 @@ def test_weight_image_forms():
     assert row0.t is w and (row0.precision, row0.layout, row0.scale_folded) == (0, 0, False)
     assert torch.equal(K.weight_image(w, 1).t, K.split_bf16x3(w))
     assert torch.equal(K.weight_image(w, 1, 2).t, K.split_bf16x3_frag(w, 2))
-    assert torch.equal(K.weight_image(w, 1, 1).t, K.split_bf16x3_frag(w, 1))
     assert torch.equal(K.weight_image(w, 0, 2).t, K.frag_f32(w))
     folded = K.weight_image(w, 1, 2, scale=sc)
     assert folded.scale_folded and torch.equal(folded.t, K.split_bf16x3_frag(w * sc[None, :, None], 2))
+    for prec in (0, 1):                                            # layout 1 (the 32 x 32 x 16 fragment order) exists at no precision
+        with pytest.raises(ValueError):
+            K.weight_image(w, prec, 1)
     with pytest.raises(ValueError):
-        K.weight_image(w, 0, 1)                                    # no fp32 image in the 32 x 32 x 16 fragment order
+        K.split_bf16x3_frag(w, 1)
 
 
 def test_untyped_operands_are_taken_as_the_image_the_launch_reads():

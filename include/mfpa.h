@@ -237,6 +237,40 @@ int mfpa_audfprint_match(const uint32_t* table, const int32_t* counts, const int
                          int search_depth, int window, int max_alignments, long long hcap, void* scratch, int K, int32_t* out,
                          int32_t* info, void* stream);
 
+/* Dejavu fingerprint store and matcher.  Integer only; results equal the reference's exactly.
+ *
+ * Table: (n_rows, 5) int32 rows [w0, w1, w2, song_id, offset], w0..w2 the 10-byte digest (sha1 hex[:20],
+ * afp/dejavu/fingerprint.py:174-213) as big-endian words with bytes 8-9 in the high half of w2; sorted by
+ * (hash, song_id, offset) and unique -- the fingerprints table of afp/dejavu/postgres_database.py:266-281 under its
+ * UNIQUE(song_id, offset, hash) constraint.  directory (2^dirbits + 1) int32: directory[b] = the first row whose leading
+ * dirbits hash bits are >= b.  dirbits in [1, 24].  song ids in [1, 2^24 - 1], offsets in [0, 2^31).
+ *
+ * mfpa_dejavu_store: INSERT ... ON CONFLICT DO NOTHING (postgres_database.py:288-295, :156-178) of a whole set of rows.
+ *   digests (n,10) uint8, sids (n) int32, offsets (n) int32; order (n) int64 = the row indices sorted by (hash, song_id,
+ *   offset) (any order among equal rows); work: max(1, ceil(n / 256)) int32; table: room for n rows; n_rows (1) int32
+ *   receives the number of unique rows written.  The table's bytes depend only on the set of rows.
+ *
+ * mfpa_dejavu_lookup: row ranges [ranges[2i], ranges[2i+1]) of the n query digests (n,10) uint8
+ *   (SELECT_MULTIPLE, postgres_database.py:212-219, one hash per IN list).
+ *
+ * mfpa_dejavu_match: CommonDatabase.return_matches (postgres_database.py:180-229) + Dejavu.align_matches
+ *   (afp/dejavu/dejavu.py:312-378) for B queries, each taken as the SET of its (hash, t1) pairs (file_recognizer.py:20-27).
+ *   digests (B,cap,10) uint8, t1 (B,cap) int32, nq (B) int32 pairs per query (the layout of mfpa_dejavu_hashes);
+ *   scratch: B * mfpa_dejavu_match_scratch_bytes(cap, hcap) bytes, hcap a power of two in [64, 2^26] (hits per query);
+ *   out (B,K,4) int32 rows [song_id, offset, count of that song's best offset, hashes_matched], count descending, ties to
+ *   the smaller song id; the best offset of a song is the smallest among its tied maxima; rows past info[2] are not
+ *   written.  info (B,4) int32 = [n_hits, n_distinct_pairs, rows written, songs hit], or [n_hits, -1, -1, -1] when
+ *   n_hits > hcap (nothing else is written: call again with a larger hcap).
+ */
+int mfpa_dejavu_store(const uint8_t* digests, const int32_t* sids, const int32_t* offsets, const int64_t* order, long long n,
+                      int dirbits, int32_t* work, int32_t* table, int32_t* n_rows, int32_t* directory, void* stream);
+int mfpa_dejavu_lookup(const int32_t* table, const int32_t* directory, int dirbits, const uint8_t* digests, int n,
+                       int32_t* ranges, void* stream);
+int mfpa_dejavu_match_scratch_bytes(int cap, long long hcap, long long* bytes);
+int mfpa_dejavu_match(const int32_t* table, const int32_t* directory, int dirbits, const uint8_t* digests, const int32_t* t1,
+                      const int32_t* nq, int B, int cap, long long hcap, void* scratch, int K, int32_t* out, int32_t* info,
+                      void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * UNet denoiser building blocks, training/unet.py:8-108.  Activations are NHWC float32
  * ("pixels x channels": H = frequency bins, W = frames); with C = 1 at both ends of the

@@ -21,7 +21,7 @@ EINVAL = -22
 EHIP = -1000
 F32, F64 = 0, 1
 STFT_TABLE_LEN = 1288
-ABI_VERSION = 40
+ABI_VERSION = 41
 
 
 class MfpaError(RuntimeError):
@@ -62,6 +62,12 @@ _SIGNATURES = {
     "mfpa_audfprint_match_scratch_bytes": ([c_longlong, c_void_p], c_int),
     "mfpa_audfprint_match": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                               c_int, c_int, c_int, c_int, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "mfpa_dejavu_store": ([c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p], c_int),
+    "mfpa_dejavu_lookup": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),
+    "mfpa_dejavu_match_scratch_bytes": ([c_int, c_longlong, c_void_p], c_int),
+    "mfpa_dejavu_match": ([c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_int,
+                           c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_conv3x3_bn_relu": ([c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                               c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p], c_int),
     "mfpa_conv3x3_c1_bn_relu": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,

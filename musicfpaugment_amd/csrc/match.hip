@@ -20,6 +20,7 @@
 //              argmax, windowed sum of the unfiltered counts, zeroing of the window, at most max_alignments + 1 modes;
 //   6. order   rows by filtered count descending, ties by (candidate rank, mode order); the first K are written.
 #include "mfpa_common.h"
+#include "mfpa_sort.h"
 
 namespace {
 
@@ -62,81 +63,12 @@ __global__ __launch_bounds__(kBlock) void store_kernel(const int32_t* __restrict
   counts[bucket] = c;
 }
 
-// Block-wide exclusive scan of one int per thread; *total gets the sum.  All threads must call it.
 __device__ __forceinline__ int block_excl_scan(int v, int* sh, int* total) {
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int off = 1; off < kBlock; off <<= 1) {
-    const int x = tid >= off ? sh[tid - off] : 0;
-    __syncthreads();
-    sh[tid] += x;
-    __syncthreads();
-  }
-  const int incl = sh[tid];
-  *total = sh[kBlock - 1];
-  __syncthreads();
-  return incl - v;
-}
-
-// Bitonic compare-exchange passes j = jstart .. 1 of stage k on s[0, len), global index of s[0] = gbase.
-__device__ __forceinline__ void lds_bitonic(unsigned long long* s, int len, long long gbase, long long k, int jstart) {
-  for (int j = jstart; j > 0; j >>= 1) {
-    for (int i = threadIdx.x; i < len; i += kBlock) {
-      const int l = i ^ j;
-      if (l > i) {
-        const bool asc = ((gbase + i) & k) == 0;
-        const unsigned long long a = s[i], b = s[l];
-        if ((a > b) == asc) {
-          s[i] = b;
-          s[l] = a;
-        }
-      }
-    }
-    __syncthreads();
-  }
+  return mfpa_sort::block_excl_scan<kBlock>(v, sh, total);
 }
 
 __device__ __forceinline__ void sort_keys(unsigned long long* keys, long long P, unsigned long long* sk) {
-  const int tid = threadIdx.x;
-  if (P <= kChunk) {
-    for (int i = tid; i < P; i += kBlock) sk[i] = keys[i];
-    __syncthreads();
-    for (long long k = 2; k <= P; k <<= 1) lds_bitonic(sk, (int)P, 0, k, (int)(k >> 1));
-    for (int i = tid; i < P; i += kBlock) keys[i] = sk[i];
-    __syncthreads();
-    return;
-  }
-  for (long long c = 0; c < P; c += kChunk) {
-    for (int i = tid; i < kChunk; i += kBlock) sk[i] = keys[c + i];
-    __syncthreads();
-    for (long long k = 2; k <= kChunk; k <<= 1) lds_bitonic(sk, kChunk, c, k, (int)(k >> 1));
-    for (int i = tid; i < kChunk; i += kBlock) keys[c + i] = sk[i];
-    __syncthreads();
-  }
-  for (long long k = 2 * kChunk; k <= P; k <<= 1) {
-    for (long long j = k >> 1; j >= kChunk; j >>= 1) {
-      for (long long i = tid; i < P; i += kBlock) {
-        const long long l = i ^ j;
-        if (l > i) {
-          const bool asc = (i & k) == 0;
-          const unsigned long long a = keys[i], b = keys[l];
-          if ((a > b) == asc) {
-            keys[i] = b;
-            keys[l] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-    for (long long c = 0; c < P; c += kChunk) {
-      for (int i = tid; i < kChunk; i += kBlock) sk[i] = keys[c + i];
-      __syncthreads();
-      lds_bitonic(sk, kChunk, c, k, kChunk >> 1);
-      for (int i = tid; i < kChunk; i += kBlock) keys[c + i] = sk[i];
-      __syncthreads();
-    }
-  }
+  mfpa_sort::sort_keys<kBlock, kChunk>(keys, P, sk);
 }
 
 __device__ __forceinline__ int key_id(unsigned long long k) { return (int)(uint32_t)(k >> 32); }

@@ -72,5 +72,12 @@ def batch(n_clips: int, seed: int = BASE_SEED, n: int = CLIP_SAMPLES, tonal: boo
     return np.stack([clip(seed + k, n, tonal) for k in range(n_clips)])
 
 
+def track(seed: int, n: int) -> np.ndarray:
+    """A long (n,) float32 recording: consecutive 8-s clips of seeds ``16 * seed + k``, cut to n samples.  Every 8-s window
+    holds tone bursts of a similar level, as music does; one long clip() puts its 6 bursts anywhere in the track."""
+    k = -(-n // CLIP_SAMPLES)
+    return np.concatenate([clip(16 * seed + j) for j in range(k)])[:n]
+
+
 def digest(a: np.ndarray) -> str:
     return hashlib.sha1(np.ascontiguousarray(a).tobytes()).hexdigest()

@@ -8,18 +8,22 @@ bf16x3 products on the bf16 matrix cores (every fp32 product as three bf16 MFMAs
 batch of synthetic clips that is already resident in HBM.  N GPUs = N processes, each with its own
 batch (weak scaling; clips are independent, no data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--clips B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--clips B] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
 (a child `python -m torch.distributed.run ...`, before this process touches the GPU) and relays rank 0's line.
-Rank 0 prints ONE JSON line; at N = 1 the headline line also carries `configs`: the other BASELINE.json
+Rank 0 prints ONE JSON line.  A plain run does only what its headline figure needs: set-up, warm-up, the timed
+steps, --dump-outputs, the line.  `roofline` is for the dominant kernel family (the MFMA implicit-GEMM
+convolutions of the UNet): algorithmic FLOPs / HIP-event time of those launches inside the timed region.
+`--full` adds everything else: at N = 1 the headline line then also carries `configs`: the other BASELINE.json
 configurations (STFT + peak-pick without the UNet for both pickers, the UNet train step, the Demucs forward)
-timed for a few steps each in the same process, each with its own `roofline`.  `roofline` is for the dominant kernel family (the MFMA implicit-GEMM
-convolutions of the UNet): algorithmic FLOPs / HIP-event time of those launches inside the timed
-region.  `cpu_baseline` times the CPU oracle (the numpy/torch-CPU restatement of the reference)
-on a bounded sample of the same workload on this box's host cores (N=1 only).
+timed for a few steps each in the same process, each with its own `roofline`; `cpu_baseline` times the CPU oracle
+(the numpy/torch-CPU restatement of the reference) on a bounded sample of the same workload on this box's host
+cores; the other arithmetic (`value_fp32`, ...), `parity_in_run`, the rocm-smi samples (`device_sample*`) and,
+without the UNet, the per-kernel `kernel_breakdown`.  At N > 1 `--full` adds the nested train-step entries
+(`dist_configs`).
 """
 from __future__ import annotations
 
@@ -828,7 +832,7 @@ def bench_infer(args, rank, world, dev, dist):
         out["parity_in_run"] = parity
     if load_sample is not None:
         out["device_sample_under_load"] = load_sample
-    if net is None and args.picker == "audfprint":
+    if net is None and args.picker == "audfprint" and args.full:
         # per-stage figures of the chain (outside the timed region; HIP events on the launch stream, 5 repetitions each): bytes the
         # stage moves per clip / its time.
         from musicfpaugment_amd import ops
@@ -897,7 +901,7 @@ def bench_launch_check(args, rank, world, dist):
            "scaling": "weak", "vs_baseline": None, "dtype": None, "data": "none",
            "config": {"workload": "none", "max_rank_seen": int(t.item())}}
     if world > 1:
-        # the shape of the N > 1 headline line: the nested train-step entries (dist_configs) with their keys, values unmeasured
+        # the shape of the N > 1 --full headline line: the nested train-step entries (dist_configs) with their keys, values unmeasured
         skel = {k: None for k in TRAIN_LINE_KEYS}
         skel.update(ranks_seen=rep["ranks_seen"], per_rank_value=rep["per_rank_value"])
         out["configs"] = {}
@@ -1175,10 +1179,14 @@ def build_parser():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--clips", type=int, default=None, help="clips per GPU per step (default 256; train / demucs-train 64)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall-time budget of each CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="infer mode: ONLY the timed chain (no other-precision leg, no parity_in_run pass, no "
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure, in the same process: the CPU baseline, the other "
+                    "arithmetic, parity_in_run, the rocm-smi samples, config 2's kernel_breakdown, the `configs` block (N = 1) or the nested "
+                    "train-step entries (N > 1).  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: wall-time budget of each CPU-baseline sample (0 = skip)")
+    ap.add_argument("--no-extras", action="store_true", help="infer mode with --full: ONLY the timed chain (no other-precision leg, no parity_in_run pass, no "
                     "under-load clock sample): counter-collection runs, where every extra launch lands in the per-kernel sums")
-    ap.add_argument("--no-configs", action="store_true", help="N = 1 infer mode: skip the `configs` block (the other BASELINE configurations)")
+    ap.add_argument("--no-configs", action="store_true", help="infer mode with --full: skip the `configs` block (the other BASELINE configurations; "
+                    "at N > 1 the nested train-step entries)")
     ap.add_argument("--no-unet", action="store_true", help="STFT + peak-pick only (BASELINE config 2 parity runs)")
     ap.add_argument("--picker", choices=["audfprint", "dejavu"], default="audfprint",
                     help="infer mode: the peak picker after the UNet (dejavu: specgram PSD, UNet output squared, 21x21 local maxima)")
@@ -1266,6 +1274,9 @@ def main():
         args.wgrad = "bf16" if args.precision in ("bf16x3", "bf16") else "fp32"
     if args.clips is None:
         args.clips = 64 if args.mode in ("train", "demucs-train") else 256
+    if not args.full:               # a plain run: only what the headline figure needs (no rocm-smi samples or kernel_breakdown either)
+        args.no_extras = args.no_configs = True
+        args.cpu_seconds = 0.0
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:       # before anything touches the GPU
         raise SystemExit(_self_launch(args.gpus, sys.argv[1:]))
@@ -1316,9 +1327,9 @@ def main():
 
     fn = {"train": bench_train, "demucs": bench_demucs, "demucs-train": bench_demucs_train, "metrics": bench_metrics,
           "infer": bench_infer}[args.mode]
-    dev_before = device_sample(local_rank) if rank == 0 else None
+    dev_before = device_sample(local_rank) if rank == 0 and args.full else None
     result = fn(args, rank, world, dev, dist)
-    dev_after = device_sample(local_rank) if rank == 0 else None
+    dev_after = device_sample(local_rank) if rank == 0 and args.full else None
     nested = None
     if world > 1 and args.mode == "infer" and not args.no_unet and not args.no_configs:
         import gc
@@ -1329,7 +1340,8 @@ def main():
         nested = dist_configs(args, rank, world, dev, dist)        # every rank: the gradient all-reduce is a collective
     if rank == 0:
         result["dist_backend"] = ("rccl (torch.distributed 'nccl')" if backend == "nccl" else backend) if dist is not None else None
-        result["device_sample"] = {"before": dev_before, "after": dev_after}      # rocm-smi on rank 0's GPU just outside the timed region
+        if args.full:
+            result["device_sample"] = {"before": dev_before, "after": dev_after}      # rocm-smi on rank 0's GPU just outside the timed region
         try:
             from musicfpaugment_amd import ops_demucs
             result["persistent_lstm_fallbacks"] = int(getattr(ops_demucs, "persistent_lstm_fallbacks", 0))

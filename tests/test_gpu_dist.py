@@ -122,7 +122,7 @@ def test_bench_runs_under_torchrun_with_two_ranks(mode):
     import json
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", MFPA_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", *RDZV, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--clips", "8",
-           "--mode", mode, *DIST_SMALL]
+           "--mode", mode, "--full", *DIST_SMALL]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     _check(r)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -148,7 +148,7 @@ def test_bench_self_launch_with_two_ranks(mode):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", MFPA_DIST_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--clips", "8", "--mode", mode, *DIST_SMALL]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--clips", "8", "--mode", mode, "--full", *DIST_SMALL]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     _check(r)
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -173,7 +173,7 @@ def test_bench_on_rccl_at_world_size_one(mode):
     env = {k: v for k, v in os.environ.items() if k != "MFPA_DIST_BACKEND"}
     env.update(MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", *RDZV, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--clips", "8",
-           "--mode", mode, "--cpu-seconds", "0", "--no-configs"]
+           "--mode", mode, "--full", "--cpu-seconds", "0", "--no-configs"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     _check(r)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

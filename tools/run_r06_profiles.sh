@@ -4,8 +4,8 @@
 export TMPDIR=/tmp
 O=gpurun_out/r06p; mkdir -p $O
 FAM=conv_mfma_kernel,convT_mfma_kernel,conv_wd16_kernel,conv_ws64_kernel,conv_up_kernel
-timeout -k 10 700 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- python3 bench.py --cpu-seconds 0 --no-configs > $O/bench_under_rocprof.json 2>> $O/bench.err
+timeout -k 10 700 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- python3 bench.py --full --cpu-seconds 0 --no-configs > $O/bench_under_rocprof.json 2>> $O/bench.err
 cp $(find $O/kt -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv; rm -rf $O/kt
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt0 -o p -- python3 bench.py --cpu-seconds 0 --no-configs --no-extras --steps 5 --warmup 1 > $O/bench_noextras_under_rocprof.json 2>> $O/bench.err
 cp $(find $O/kt0 -name "*kernel_stats.csv" | head -1) $O/bench_noextras_kernel_stats.csv; rm -rf $O/kt0
@@ -27,14 +27,14 @@ python tools/sq_table.py $O/pmc_sq_pass1.json $O/pmc_sq_pass2.json > $O/pmc_sq_t
 rm -rf $O/pmc_s1 $O/pmc_s2 $O/pmc_s3
 python tools/exp_upconv.py --clips 64 2>&1 | grep -v amdgpu > $O/upconv_levels.txt
 python tools/exp_upconv.py --clips 64 --precision 0 --reps 3 2>&1 | grep -v amdgpu > $O/upconv_levels_fp32.txt
-timeout -k 10 300 python bench.py --mode train --precision bf16 --wgrad bf16 --augment --steps 20 --warmup 5 > $O/train_step_bf16_bench_line.json 2>> $O/bench.err
-timeout -k 10 300 python bench.py --mode train --precision bf16 --wgrad bf16 --steps 20 --warmup 5 > $O/train_step_bf16_premixed_bench_line.json 2>> $O/bench.err
-timeout -k 10 300 python bench.py --mode demucs --steps 20 --warmup 5 > $O/demucs_bench_line.json 2>> $O/bench.err
+timeout -k 10 300 python bench.py --full --mode train --precision bf16 --wgrad bf16 --augment --steps 20 --warmup 5 > $O/train_step_bf16_bench_line.json 2>> $O/bench.err
+timeout -k 10 300 python bench.py --full --mode train --precision bf16 --wgrad bf16 --steps 20 --warmup 5 > $O/train_step_bf16_premixed_bench_line.json 2>> $O/bench.err
+timeout -k 10 300 python bench.py --full --mode demucs --steps 20 --warmup 5 > $O/demucs_bench_line.json 2>> $O/bench.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktt -o p -- python3 bench.py --mode train --precision bf16 --wgrad bf16 --augment --steps 10 --warmup 3 --cpu-seconds 0 > $O/train_step_bf16_bench_under_rocprof.json 2>> $O/bench.err
 cp $(find $O/ktt -name "*kernel_stats.csv" | head -1) $O/train_step_bf16_kernel_stats.csv; rm -rf $O/ktt
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktd -o p -- python3 bench.py --mode demucs --steps 10 --warmup 3 --cpu-seconds 0 > $O/demucs_bench_under_rocprof.json 2>> $O/bench.err
 cp $(find $O/ktd -name "*kernel_stats.csv" | head -1) $O/demucs_kernel_stats.csv; rm -rf $O/ktd
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt2 -o p -- python3 bench.py --no-unet --steps 20 --warmup 3 > $O/config2_bench_under_rocprof.json 2>> $O/bench.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt2 -o p -- python3 bench.py --full --no-unet --steps 20 --warmup 3 > $O/config2_bench_under_rocprof.json 2>> $O/bench.err
 cp $(find $O/kt2 -name "*kernel_stats.csv" | head -1) $O/config2_kernel_stats.csv; rm -rf $O/kt2
 python tools/exp_lstm.py 2>&1 | grep -v amdgpu > $O/demucs_lstm_step.txt
 python tools/time_small_kernels.py 2>&1 | grep -v amdgpu > $O/small_kernels.txt

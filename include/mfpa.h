@@ -619,8 +619,8 @@ typedef struct mfpa_gemm_desc {
   int precision;   /* 0: fp32 MFMA (K multiple of 16); 1: bf16x3 where K >= 128 is a multiple of 32 or K is 48 / 96 (fp32 MFMA otherwise);
                     * 2: bf16x3 with W ALREADY split -- every 32-element chunk of a row as [32 bf16 hi | 32 bf16 lo], w = hi + lo -- for
                     * weights that do not change between calls (K >= 128 a multiple of 32, npad a multiple of 128, no c1_x) */
-  /* optional (K <= 256, fp32 kernel): A is COMPUTED while it is staged as the first encoder layer of
-   * mfpa_conv1d_c1_relu -- A[b][m][c] = relu(c1_b[c] + sum_j c1_w[j][c] * c1_x[b][4m + j]), c1_x (batch, c1_lin), c1_w (8, K) --
+  /* optional (K <= 256, fp32 kernel): A is COMPUTED while it is staged as the first encoder layer Conv1d(1 -> K, k8, s4) + ReLU
+   * -- A[b][m][c] = relu(c1_b[c] + sum_j c1_w[j][c] * c1_x[b][4m + j]), c1_x (batch, c1_lin), c1_w (8, K) --
    * so its (B, L, K) output never exists in HBM (model.py:231-238); A may then be NULL. */
   const float* c1_x; long long c1_lin; const float* c1_w; const float* c1_b;
   float* C2; long long ldc2, strideC2;
@@ -635,11 +635,9 @@ int mfpa_demucs_prep(const float* wav, int B, int T, int VL, float floor_, float
 int mfpa_upsample2(const float* x, int B, int T, const float* kernel112, float* y, void* stream);
 int mfpa_downsample2(const float* x, int B, int T, const float* kernel112, float* y, int To, const float* scale,
                      int Tkeep, void* stream);
-/* First encoder layer Conv1d(1->C, k8, s4)+ReLU: x (B,Lin) -> y (B,Lout,C), w (8,C) tap-major. */
-int mfpa_conv1d_c1_relu(const float* x, int B, int Lin, int Lout, int C, const float* w, const float* bias, float* y,
-                        void* stream);
-/* The same without the ReLU when relu == 0 (bias may be NULL): with x = the gradient of the last ConvTranspose1d's output
- * and w = its (8, C) taps this is that layer's input gradient. */
+/* First encoder layer Conv1d(1->C, k8, s4), + ReLU when relu != 0: x (B,Lin) -> y (B,Lout,C), w (8,C) tap-major, bias (C) or
+ * NULL.  Without the ReLU and the bias, with x = the gradient of the last ConvTranspose1d's output and w = its (8, C) taps, this
+ * is that layer's input gradient. */
 int mfpa_conv1d_c1(const float* x, int B, int Lin, int Lout, int C, const float* w, const float* bias, int relu, float* y,
                    void* stream);
 /* Last decoder layer ConvTranspose1d(C->1, k8, s4): P (B,L+2,C) with zero first/last rows -> y (B, 4(L+1)), w (8,C). */
@@ -659,13 +657,10 @@ int mfpa_glu_convT1d_c1(const float* x, int B, int L, int C, const float* gw, co
                         void* stream);
 /* The same with the bias read from device memory (training: the optimiser updates it there). */
 int mfpa_convT1d_c1_dev(const float* P, int B, int L, int C, const float* w, const float* bias_dev, float* y, void* stream);
-/* LSTM cell (gate order i,f,g,o; model.py:91-110 via nn.LSTM): gates (B,4H) rows ldg apart, c (B,H) in/out,
- * hout rows ldh apart; optional hsum = h + addend (the first decoder skip). */
-int mfpa_lstm_cell(const float* gates, long long ldg, float* c, int B, int H, float* hout, long long ldh, float* hsum,
-                   const float* addend, long long ldadd, void* stream);
 
-/* One LSTM time step in ONE launch: gates = hprev W_hh^T + xp (hprev NULL at t = 0: gates = xp), then the cell update of
- * mfpa_lstm_cell.  whh_grouped = W_hh (4H,H) with rows regrouped to [H/16][i16|f16|g16|o16][H] so a workgroup owns all
+/* One LSTM time step in ONE launch: gates = hprev W_hh^T + xp (hprev NULL at t = 0: gates = xp), then the cell update (gate
+ * order i,f,g,o; model.py:91-110 via nn.LSTM): c (B,H) in/out, hout rows ldh apart; optional hsum = h + addend (the first
+ * decoder skip).  whh_grouped = W_hh (4H,H) with rows regrouped to [H/16][i16|f16|g16|o16][H] so a workgroup owns all
  * four gates of its 16 hidden units; xp (B,4H) in the standard gate order, rows ldxp apart, includes both biases.
  * bf16x3 products, fp32 accumulate.  H multiple of 128. */
 int mfpa_lstm_step(const float* hprev, long long ldhp, const float* whh_grouped, const float* xp, long long ldxp, float* c,
@@ -716,17 +711,12 @@ int mfpa_c1_wgrad(const float* x, long long ldx, const float* g, long long ldg, 
 int mfpa_downsample2_adjoint(const float* dy, int B, int ldy, int nout, const float* kernel112, const float* scale, int T, float* dx,
                              void* stream);
 
-/* Whole-layer forms (one call across the ABI for the Tn launches): (B, Tn, .) contiguous buffers.  mfpa_lstm_layer: xp (B,Tn,4H)
- * input projections incl. biases; inference (train = 0): cstate (B,H) scratch, cseq unused; train = 1: cseq (B,Tn,H) receives
- * c_t and xp is overwritten with the gate activations; xsum / skip as in mfpa_lstm_step (NULL for the first layer).
- * mfpa_lstm_layer_bwd: gates <- gate pre-activation gradients, dcstate (B,H) scratch. */
-int mfpa_lstm_layer(const float* whh_grouped, float* xp, float* hseq, float* cseq, float* cstate, int B, int Tn, int H, float* xsum,
-                    const float* skip, int train, void* stream);
-int mfpa_lstm_layer_bwd(const float* whhT, float* gates, const float* cseq, const float* dhout, float* dcstate, int B, int Tn, int H,
-                        void* stream);
-/* The same for the time steps [t0, t1) only (backward: t1-1 down to t0), so that the two layers can run as a pipeline on two
- * streams: layer 1 works on chunk k while layer 0 is already on chunk k+1 (backward: the other way round).  The state buffers
- * (cstate / dcstate) are zeroed by the call that holds the first step of the recurrence. */
+/* Whole-layer forms (one call across the ABI for the launches of time steps [t0, t1); backward: t1-1 down to t0): (B, Tn, .)
+ * contiguous buffers.  mfpa_lstm_layer_range: xp (B,Tn,4H) input projections incl. biases; inference (train = 0): cstate (B,H)
+ * scratch, cseq unused; train = 1: cseq (B,Tn,H) receives c_t and xp is overwritten with the gate activations; xsum / skip as in
+ * mfpa_lstm_step (NULL for the first layer).  mfpa_lstm_layer_bwd_range: gates <- gate pre-activation gradients, dcstate (B,H)
+ * scratch.  A sub-range lets the two layers run as a pipeline on two streams: layer 1 works on chunk k while layer 0 is already
+ * on chunk k+1.  The state buffers (cstate / dcstate) are zeroed by the call that holds the first step of the recurrence. */
 int mfpa_lstm_layer_range(const float* whh_grouped, float* xp, float* hseq, float* cseq, float* cstate, int B, int Tn, int H,
                           float* xsum, const float* skip, int train, int t0, int t1, void* stream);
 int mfpa_lstm_layer_bwd_range(const float* whhT, float* gates, const float* cseq, const float* dhout, float* dcstate, int B, int Tn,

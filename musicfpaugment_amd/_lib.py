@@ -21,7 +21,7 @@ EINVAL = -22
 EHIP = -1000
 F32, F64 = 0, 1
 STFT_TABLE_LEN = 1288
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 
 class MfpaError(RuntimeError):
@@ -95,7 +95,6 @@ _SIGNATURES = {
     "mfpa_demucs_prep": ([c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_upsample2": ([c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_downsample2": ([c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
-    "mfpa_conv1d_c1_relu": ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_convT1d_c1": ([c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p], c_int),
     "mfpa_convT1d_c1_dev": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_loss_blocks": ([], c_int),
@@ -107,17 +106,12 @@ _SIGNATURES = {
     "mfpa_reflect_pad_adjoint": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
     "mfpa_lstm_step": ([c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_int, c_void_p, c_longlong,
                         c_void_p, c_void_p, c_longlong, c_void_p], c_int),
-    "mfpa_lstm_cell": ([c_void_p, c_longlong, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p, c_void_p,
-                        c_longlong, c_void_p], c_int),
     "mfpa_conv1d_c1": ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
     "mfpa_lstm_step_train": ([c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong,
                               c_int, c_int, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_longlong,
                               c_void_p], c_int),
     "mfpa_lstm_step_bwd": ([c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong,
                             c_void_p, c_longlong, c_void_p, c_int, c_int, c_void_p], c_int),
-    "mfpa_lstm_layer": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
-                        c_int),
-    "mfpa_lstm_layer_bwd": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p], c_int),
     "mfpa_lstm_layer_range": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                c_int, c_void_p], c_int),
     "mfpa_conv1d_c1_glu": ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),

@@ -9,13 +9,13 @@
 //                             end), N = 4*Cout: output row t is positions 4t..4t+3 -- the overlap-add of the
 //                             transposed convolution becomes part of K; the skip connection of the next decoder
 //                             layer is added in the epilogue
-//   LSTM                    : input projection of all steps as one GEMM; per step gates = h[t-1] W_hh^T + X[t]
-//                             (the same kernel, rows = clips) followed by the cell kernel
+//   LSTM                    : input projection of all steps as one GEMM; the recurrence gates = h[t-1] W_hh^T + X[t] and
+//                             the cell update in one persistent launch per layer (lstm_seq_kernel), or one launch per step
+//                             (lstm_step_kernel) where the persistent grid cannot be resident
 // The 1-channel ends (first Conv1d, last ConvTranspose1d), the sinc x2 resamplers and the std normalisation are
 // small VALU kernels.
 #include "mfpa_common.h"
 #include <type_traits>
-#include <cstdlib>
 
 namespace {
 
@@ -32,8 +32,7 @@ struct GemmArgs {
   const float* bias;                           // [Npad] or null
   const float* addend; long long ldadd, strideAdd;   // mode 2: y += addend[b*strideAdd + m*ldadd + n]
   float* C; long long ldc, strideC;
-  int exp;                                     // experiments only (MFPA_EXP_FLAG): bit 0 / 1 = every K chunk re-reads chunk 0 of A / W
-  int nx, ny, nz, xcd;                         // tile grid (n tiles, m tiles, clips) of the 1-D launch; xcd = 1: XCD-aware tile order
+  int nx, ny, nz;                              // tile grid (n tiles, m tiles, clips) of the 1-D launch
   float* C2; long long ldc2, strideC2;         // training: second output (mode 1: the packed GLU pre-activations; relu 2: relu(y) before the addition)
   int M, N, K, mode, relu;                     // mode 0: bias(+relu); 1: GLU (N = output columns = Npad_total/2 pairs); 2: + addend;
                                                // 3: * (addend > 0) -- the ReLU backward mask of the layer that produced addend
@@ -49,12 +48,9 @@ struct GemmArgs {
 // n tile) order, n fastest, so the workgroups sharing an A tile run back to back on ONE XCD.
 __device__ __forceinline__ bool gemm_tile_at(const GemmArgs& a, unsigned vb, int& bx, int& by, int& bz) {
   const unsigned total = (unsigned)a.nx * a.ny * a.nz;
-  unsigned lin = vb;
-  if (a.xcd) {
-    const unsigned per = (total + 7) / 8;
-    if (vb / 8 >= per) return false;           // past the last virtual id (a persistent workgroup stepping by gridDim.x): NOT the next XCD's range
-    lin = (vb % 8) * per + vb / 8;
-  }
+  const unsigned per = (total + 7) / 8;
+  if (vb / 8 >= per) return false;             // past the last virtual id (a persistent workgroup stepping by gridDim.x): NOT the next XCD's range
+  const unsigned lin = (vb % 8) * per + vb / 8;
   if (lin >= total) return false;              // uniform over the workgroup, before any barrier
   bx = lin % a.nx;
   const unsigned rest = lin / a.nx;
@@ -576,9 +572,9 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16x3_pipe_kernel(GemmArgs a) {
   Stage st0, st1;
   auto load = [&](const TileP& t, int kc, Stage& st) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) st.a[i] = *reinterpret_cast<const f32x4*>(t.ap[i] + (MFPA_EXP_FLAG(a.exp, 1) ? 0 : kc) * HKC);
+    for (int i = 0; i < 4; ++i) st.a[i] = *reinterpret_cast<const f32x4*>(t.ap[i] + kc * HKC);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) st.b[i] = *reinterpret_cast<const f32x4*>(t.bp[i] + (MFPA_EXP_FLAG(a.exp, 2) ? 0 : kc) * HKC);
+    for (int i = 0; i < 2; ++i) st.b[i] = *reinterpret_cast<const f32x4*>(t.bp[i] + kc * HKC);
   };
   auto split_store = [&](char* row, f32x4 v) __attribute__((always_inline)) {
     g_bf16x4 hi, lo;
@@ -592,13 +588,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16x3_pipe_kernel(GemmArgs a) {
   };
   auto store = [&](int buf, const Stage& st) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#ifdef MFPA_GEMM_ACOPY   // timing-only variant (wrong results by design): the activation tile is COPIED into LDS as if it arrived already split
-      *reinterpret_cast<f32x4*>(As + buf * ASZ + (r0 + 64 * i) * HROW + 16 * q) = st.a[i];
-#else
-      split_store(As + buf * ASZ + (r0 + 64 * i) * HROW, st.a[i]);
-#endif
-    }
+    for (int i = 0; i < 4; ++i) split_store(As + buf * ASZ + (r0 + 64 * i) * HROW, st.a[i]);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       if (WSPLIT) *reinterpret_cast<f32x4*>(Bs + buf * BSZ + (r0 + 64 * i) * HROW + 16 * q) = st.b[i];
@@ -1040,13 +1030,12 @@ __global__ __launch_bounds__(256, 2) void c1_glu_kernel(const float* __restrict_
         const int row = cr + 21 * p;
         if (row < 128) {
           f32x4 v = wq[8];
-#ifndef MFPA_HEAD_PACKED_FMA
           // One v_fma_f32 per element, kept from being paired (the empty asm).  Written as `v += x * wq[j]` hipcc emits
           // v_pk_fma_f32 with op_sel:[0,1,0] (the LOW lane takes the HIGH half of the sample pair) for the odd samples, and with
           // TWO workgroups per CU -- i.e. while the SIMD's other wave runs MFMAs -- the low lane of those instructions sporadically
           // came out wrong: wrong rows of A, different from run to run, only at > 256 workgroups; bit-exact with one workgroup per
           // CU, with this form, and in the 128 x 64-tile GEMM form, whose loader only uses the op_sel_hi:[1,0,1] broadcast
-          // (profiles/r02_pk_fma_op_sel.md; -DMFPA_HEAD_PACKED_FMA + tools/probes/head_kernel_two_wg_per_cu.py reproduce it).
+          // (profiles/r02_pk_fma_op_sel.md; tests/test_isa_scan.py keeps the packed form out of the library).
 #pragma unroll
           for (int j = 0; j < 8; ++j)
 #pragma unroll
@@ -1055,24 +1044,6 @@ __global__ __launch_bounds__(256, 2) void c1_glu_kernel(const float* __restrict_
               asm volatile("" : "+v"(t));
               v[k] = t;
             }
-#elif MFPA_HEAD_PACKED_FMA == 2
-          // packed FMAs WITHOUT operand selection: every sample is first materialised as an {x, x} pair (experiment)
-          {
-            typedef float hf2 __attribute__((ext_vector_type(2)));
-            hf2 v01 = {v[0], v[1]}, v23 = {v[2], v[3]};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              hf2 xx = {xr[p][j >> 2][j & 3], xr[p][j >> 2][j & 3]};
-              asm volatile("" : "+v"(xx));
-              v01 += xx * hf2{wq[j][0], wq[j][1]};
-              v23 += xx * hf2{wq[j][2], wq[j][3]};
-            }
-            v = f32x4{v01[0], v01[1], v23[0], v23[1]};
-          }
-#else
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v += xr[p][j >> 2][j & 3] * wq[j];
-#endif
 #pragma unroll
           for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
           split_store(As + row * ROW, cq, v);
@@ -1265,25 +1236,6 @@ __global__ __launch_bounds__(256) void convT1d_c1_kernel(const float* __restrict
   }
 }
 
-// LSTM cell (gate order i, f, g, o): c = sig(f) c + sig(i) tanh(g); h = sig(o) tanh(c).
-// gates (B, 4H); c (B, H) in/out; h written to hseq[b*ldh + n] (+ optional addend for the decoder's first skip).
-__global__ __launch_bounds__(256) void lstm_cell_kernel(const float* __restrict__ gates, long long ldg, float* __restrict__ c, int B, int H,
-                                                        float* __restrict__ hout, long long ldh,
-                                                        float* __restrict__ hsum, const float* __restrict__ addend, long long ldadd) {
-  const int total = B * H;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < total; e += gridDim.x * 256) {
-    const int b = e / H, n = e % H;
-    const float* g = gates + (size_t)b * ldg;
-    const float gi = g[n], gf = g[H + n], gg = g[2 * H + n], go = g[3 * H + n];
-    const float si = 1.f / (1.f + expf(-gi)), sf = 1.f / (1.f + expf(-gf)), so = 1.f / (1.f + expf(-go));
-    const float cn = sf * c[e] + si * tanhf(gg);
-    c[e] = cn;
-    const float h = so * tanhf(cn);
-    hout[(size_t)b * ldh + n] = h;
-    if (hsum) hsum[(size_t)b * ldh + n] = h + addend[(size_t)b * ldadd + n];
-  }
-}
-
 // ---------------------------------------------------------------------------------- fused LSTM time step
 // One launch per time step: gates = h[t-1] W_hh^T (+ xp[t], the input projection incl. both biases) AND the cell update,
 // so the recurrence costs one short kernel per step instead of a GEMM + a cell kernel.
@@ -1300,10 +1252,7 @@ constexpr int LROW = 4 * LKC + 16;       // LDS row bytes: [128 hi | 128 lo | pa
 constexpr int LU = 16;                   // hidden units per workgroup (64 gate columns)
 
 constexpr int LTHREADS = 512;   // 8 waves: (clip half) x (gate-column half) x (k-step half of every chunk)
-#ifndef MFPA_LSTM_PF
-#define MFPA_LSTM_PF 3
-#endif
-constexpr int LPF = MFPA_LSTM_PF;  // chunks of global loads in flight per thread (register ring)
+constexpr int LPF = 3;          // chunks of global loads in flight per thread (register ring)
 
 // MT = 32-clip tiles per workgroup: 2 (64 clips; 8 waves = 2 clip halves x 2 gate-column halves x 2 k-step halves) or 1 (32
 // clips; 2 gate-column halves x 4 k-step quarters).  The step streams h[t-1] and its W_hh slice from memory every launch and is
@@ -1460,10 +1409,8 @@ __global__ __launch_bounds__(LTHREADS, 1) void lstm_step_kernel(const float* __r
 static int lstm_launch(const float* hprev, long long ldhp, const float* whh_grouped, const float* xp, long long ldxp, const float* cin,
                        long long ldci, float* cout, long long ldco, int B, int H, float* hout, long long ldh, float* hsum,
                        const float* addend, long long ldadd, float* gsave, long long ldgs, void* stream) {
-  static const int force = MFPA_EXP_ENV("MFPA_LSTM_MT", 0);
   const int groups = H / LU;
-  int MT = ((long long)groups * ((B + 31) / 32) <= 256) ? 1 : 2;
-  if (force == 1 || force == 2) MT = force;
+  const int MT = ((long long)groups * ((B + 31) / 32) <= 256) ? 1 : 2;
   const int mtiles = (B + 32 * MT - 1) / (32 * MT);
   const long long total = (long long)groups * mtiles;
   if (total > 0x7fffff) return MFPA_EINVAL;
@@ -1512,11 +1459,10 @@ struct LstmSeqArgs {
   unsigned* sync;         // LSTM_SYNC_WORDS words
   char* hsplit;           // [2][B][H * 4 bytes]
   int B, Tn, H, t0, t1, train, nslab, ngroups;
-  int dbg;                // -DMFPA_EXPERIMENTS builds only (MFPA_LSTM_DBG, timing experiments: results are wrong): 1 no MFMAs, 2 no loads of h, 4 no waits, 8 no s_sleep in the poll
 };
 
-// COH 0: the waiting thread invalidates L1 / L2 once per step and h is read with ordinary (cached) loads; 1: no invalidate, h is read
-// with agent-scope (sc1) buffer loads that do not trust the local caches.
+// h[t-1] is read with agent-scope (sc1) buffer loads that do not trust the local caches, so a step needs no L1 / L2 invalidate
+// (an invalidate per step + cached loads measured 7.83 vs 7.58 ms for both layers of 256 clips).
 // MS = 32-clip MFMA row tiles per workgroup (slab = 32 MS clips): 2 for large batches; 1 while that still leaves half the chip free --
 // twice the workgroups, each reading half as much of h per step (the step is bound by what a CU can pull, see the timing experiments).
 template <int N> struct LFV { float v[N]; __device__ __forceinline__ float& operator[](int i) { return v[i]; } __device__ __forceinline__ const float& operator[](int i) const { return v[i]; } };
@@ -1528,36 +1474,19 @@ template <int N> __device__ __forceinline__ void lfv_store(float* p, const LFV<N
 #pragma unroll
   for (int i = 0; i < N; ++i) p[i] = x.v[i]; }
 
-#ifndef MFPA_LSTM_WIDE_PUT
-#define MFPA_LSTM_WIDE_PUT 1      // round 6: a step's new h leaves the workgroup as 16-byte write-through stores (gathered through LDS) instead of one
-#endif                            // 4-byte (2-byte) agent-scope store per cell thread and half: narrow sc1 stores are one fabric write each (A/B builds: 0)
-#ifndef MFPA_LSTM_FAST_CELL
-#define MFPA_LSTM_FAST_CELL 1     // round 6: the cell's sigmoid / tanh on v_exp_f32 + v_rcp_f32 (absolute error ~1e-7) instead of the library expf / tanhf (A/B builds: 0)
-#endif
-__device__ __forceinline__ float lstm_sig(float x) {
-#if MFPA_LSTM_FAST_CELL
-  return __builtin_amdgcn_rcpf(1.f + __expf(-x));
-#else
-  return 1.f / (1.f + expf(-x));
-#endif
-}
+// The cell's sigmoid / tanh on v_exp_f32 + v_rcp_f32 (absolute error ~1e-7), not the library expf / tanhf.
+__device__ __forceinline__ float lstm_sig(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float lstm_tanh(float x) {
-#if MFPA_LSTM_FAST_CELL
   return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x));       // e^{2x} -> inf: 1; -> 0: -1
-#else
-  return tanhf(x);
-#endif
 }
 
-template <int KS, int COH, int MS>          // k-steps of 16 per wave: H = 128 KS
+template <int KS, int MS>          // k-steps of 16 per wave: H = 128 KS
 __global__ __launch_bounds__(64 * QW, 1) void lstm_seq_kernel(LstmSeqArgs a) {
   constexpr int SLAB = 32 * MS, UPT = MS, TPC = 16 / UPT;   // clips per workgroup; hidden units per cell thread; cell threads per clip
   typedef LFV<UPT> fv;
   extern __shared__ __attribute__((aligned(16))) char lsm[];
   float* G = reinterpret_cast<float*>(lsm);                 // [QW][SLAB][QGLD]
-#if MFPA_LSTM_WIDE_PUT
   char* const PS = lsm + (size_t)QW * SLAB * QGLD * sizeof(float);   // [SLAB][64 B]: the step's new h, split, on its way out
-#endif
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int H = a.H;
@@ -1649,10 +1578,9 @@ __global__ __launch_bounds__(64 * QW, 1) void lstm_seq_kernel(LstmSeqArgs a) {
             dead = true;
             break;
           }
-          if (!MFPA_EXP_FLAG(a.dbg, 8)) __builtin_amdgcn_s_sleep(1);
+          __builtin_amdgcn_s_sleep(1);
         }
       }
-      if (!COH) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // one invalidate per step: the loads of h below go through L1 / L2
     }
     __syncthreads();
   };
@@ -1679,8 +1607,7 @@ __global__ __launch_bounds__(64 * QW, 1) void lstm_seq_kernel(LstmSeqArgs a) {
       for (int g = 0; g < 4; ++g) xg[g] = lfv_load<UPT>(xr + g * H);
       if (a.xsum) ad = lfv_load<UPT>(a.skip + (size_t)m * ldh + (size_t)t * H + u0);
     }
-    if (!MFPA_EXP_FLAG(a.dbg, 4)) wait((unsigned)(t - a.t0 + 1));
-    const char* hp = a.hsplit + (size_t)((t + 1) & 1) * bufb;
+    wait((unsigned)(t - a.t0 + 1));
     floatx16 acc[MS][2];
 #pragma unroll
     for (int i = 0; i < 2 * MS; ++i)
@@ -1691,17 +1618,9 @@ __global__ __launch_bounds__(64 * QW, 1) void lstm_seq_kernel(LstmSeqArgs a) {
 #pragma unroll
       for (int mt = 0; mt < MS; ++mt) {
         const size_t off = arow[mt] + (size_t)(s >> 1) * 128 + (size_t)(s & 1) * 32;
-        if (MFPA_EXP_FLAG(a.dbg, 2)) {
-          f[mt][0] = wh[0][0]; f[mt][1] = wl[0][0];
-        } else if (COH) {
-          typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-          const unsigned o = (unsigned)(((t + 1) & 1) * bufb + off);
-          f[mt][0] = __builtin_bit_cast(l_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(hrsrc, o, 0, 16));
-          f[mt][1] = __builtin_bit_cast(l_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(hrsrc, o + 64, 0, 16));
-        } else {
-          f[mt][0] = *reinterpret_cast<const l_bf16x8*>(hp + off);
-          f[mt][1] = *reinterpret_cast<const l_bf16x8*>(hp + off + 64);
-        }
+        const unsigned o = (unsigned)(((t + 1) & 1) * bufb + off);
+        f[mt][0] = __builtin_bit_cast(l_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(hrsrc, o, 0, 16));
+        f[mt][1] = __builtin_bit_cast(l_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(hrsrc, o + 64, 0, 16));
       }
     };
 #pragma unroll
@@ -1712,7 +1631,6 @@ __global__ __launch_bounds__(64 * QW, 1) void lstm_seq_kernel(LstmSeqArgs a) {
       for (int mt = 0; mt < MS; ++mt)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-          if (MFPA_EXP_FLAG(a.dbg, 1)) { acc[mt][nt][0] += (float)fa[s % PF][mt][0][0] + (float)fa[s % PF][mt][1][0]; continue; }
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s % PF][mt][1], wh[nt][s], acc[mt][nt], 0, 0, 0);
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s % PF][mt][0], wl[nt][s], acc[mt][nt], 0, 0, 0);
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s % PF][mt][0], wh[nt][s], acc[mt][nt], 0, 0, 0);
@@ -1750,7 +1668,6 @@ __global__ __launch_bounds__(64 * QW, 1) void lstm_seq_kernel(LstmSeqArgs a) {
         hs[k] = hn[k] + ad[k];
         vi[k] = si; vf[k] = sf; vg[k] = tg; vo[k] = so;
       }
-#if MFPA_LSTM_WIDE_PUT
       {   // this thread's hi / lo halves into the workgroup's staging rows: [clip][16 units x bf16 hi | 16 units x bf16 lo]
         char* ps = PS + clip * 64 + UPT * up * 2;
         if (UPT == 2) {
@@ -1764,9 +1681,6 @@ __global__ __launch_bounds__(64 * QW, 1) void lstm_seq_kernel(LstmSeqArgs a) {
           *reinterpret_cast<unsigned short*>(ps + 32) = __builtin_bit_cast(unsigned short, (__bf16)(hn[0] - (float)h0));
         }
       }
-#else
-      put_split(a.hsplit + (size_t)(t & 1) * bufb, hn);
-#endif
       const size_t o = (size_t)m * ldh + (size_t)t * H + u0;
       lfv_store<UPT>(a.hseq + o, hn);
       if (a.xsum) lfv_store<UPT>(a.xsum + o, hs);
@@ -1779,9 +1693,8 @@ __global__ __launch_bounds__(64 * QW, 1) void lstm_seq_kernel(LstmSeqArgs a) {
         lfv_store<UPT>(a.cseq + o, c);
       }
     }
-#if MFPA_LSTM_WIDE_PUT
     if (t + 1 < a.t1) {
-      // the slab's new h as 16-byte write-through (sc1) stores: thread j takes piece j & 3 (hi 0..7, hi 8..15, lo 0..7, lo 8..15) of clip j >> 2
+      // the slab's new h as 16-byte write-through (sc1) stores (gathered through LDS: narrow sc1 stores are one fabric write each): thread j takes piece j & 3 (hi 0..7, hi 8..15, lo 0..7, lo 8..15) of clip j >> 2
       __syncthreads();
       if (tid < 4 * SLAB) {
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -1797,9 +1710,6 @@ __global__ __launch_bounds__(64 * QW, 1) void lstm_seq_kernel(LstmSeqArgs a) {
       }
       arrive();
     }
-#else
-    if (t + 1 < a.t1) arrive();                            // (its __syncthreads also frees the gate slabs for the next step)
-#endif
   }
   if (live && !a.train) lfv_store<UPT>(a.cstate + (size_t)m * H + u0, c);
 }
@@ -1812,9 +1722,7 @@ static int lstm_seq_plan(int B, int H, int wg_budget, int* ms_out) {
   const int cus = lstm_seq_cus();
   const int budget = (wg_budget > 0 && wg_budget < cus) ? wg_budget : cus;
   const int ks = H / 128, ngroups = H / LU;
-  static const int force_ms = MFPA_EXP_ENV("MFPA_LSTM_MS", 0);
-  int ms = ((long long)((B + 31) / 32) * ngroups <= (budget < cus / 2 ? budget : cus / 2)) ? 1 : 2;
-  if (force_ms == 1 || force_ms == 2) ms = force_ms;
+  const int ms = ((long long)((B + 31) / 32) * ngroups <= (budget < cus / 2 ? budget : cus / 2)) ? 1 : 2;
   const int nslab = (B + 32 * ms - 1) / (32 * ms);
   if (ms_out) *ms_out = ms;
   if (H % 128 || !(ks == 2 || ks == 4 || ks == 6 || ks == 8) || nslab > 32 || (long long)B * H * 8 > 0x7fffffffLL ||
@@ -1828,6 +1736,8 @@ static int lstm_seq_plan(int B, int H, int wg_budget, int* ms_out) {
 extern "C" {
 
 #define SK_LDS(KCW) ((size_t)(GBM + GBN) * (4 * (KCW) + 16))
+constexpr int PIPE_MIN_M = 192;   // rows per clip from which the pipelined 256 x 128 kernel serves (rows past M are clamped when loaded: a 249-row clip fills 97 % of a 256-row tile)
+
 int mfpa_gemm_mfma(const mfpa_gemm_desc* d, void* stream) {
   if (!d) return MFPA_EINVAL;
   if (d->batch == 0 || d->M == 0) return MFPA_OK;
@@ -1849,9 +1759,7 @@ int mfpa_gemm_mfma(const mfpa_gemm_desc* d, void* stream) {
   a.C2 = d->C2; a.ldc2 = d->ldc2; a.strideC2 = d->strideC2;
   a.M = d->M; a.N = d->N; a.K = d->K; a.mode = d->mode; a.relu = d->relu;
   a.c1_x = d->c1_x; a.c1_lin = d->c1_lin; a.c1_w = d->c1_w; a.c1_b = d->c1_b;
-  static const int xcd_env = MFPA_EXP_ENV("MFPA_GEMM_XCD", 1);   // 0: plain tile order (experiments)
-  a.ny = (d->M + GBM - 1) / GBM; a.nz = d->batch; a.nx = d->npad / GBN; a.xcd = xcd_env;
-  a.exp = MFPA_EXP_ENV("MFPA_GEMM_EXP", 0);
+  a.ny = (d->M + GBM - 1) / GBM; a.nz = d->batch; a.nx = d->npad / GBN;
   if ((long long)a.nx * a.ny * a.nz > 0x3fffffffLL) return MFPA_EINVAL;
   auto grid1d = [&](int nx) { a.nx = nx; return dim3((unsigned)((((long long)nx * a.ny * a.nz + 7) / 8) * 8)); };
   dim3 grid = grid1d(d->npad / GBN);
@@ -1860,39 +1768,34 @@ int mfpa_gemm_mfma(const mfpa_gemm_desc* d, void* stream) {
   // K >= 128: the chunked bf16x3 kernel.  (At first the K = 128 / 192 levels ran faster on the fp32 kernel; that was the
   // epilogue's serialised addend loads and 64-bit addressing, not the arithmetic: with those fixed the fp32 MFMA rate is what
   // bounds them -- PMC: 2.2 of 4.0 ms MFMA-busy on the K = 192 transposed convolution -- and bf16x3 is 10 % faster end to end.)
-  static const int shortk = MFPA_EXP_ENV("MFPA_SHORTK", 1);   // 0: the fp32-MFMA kernels for K < 256 (experiments)
   hipStream_t st = mfpa_stream(stream);
-  static const int wide = MFPA_EXP_ENV("MFPA_GEMM_WIDE", 1);   // 0: always the 128 x 64 tile (experiments)
-  static const int pipe = MFPA_EXP_ENV("MFPA_GEMM_PIPE", 1);   // 0: the 128 x 128 kernel without the software pipeline (experiments)
-  const bool wide_ok = d->K % HKC == 0 && d->K >= 128 && d->npad % WBN == 0 && (d->precision == 2 || (d->precision == 1 && wide));
-  if (wide_ok && pipe && d->K % (2 * HKC) == 0 && d->M >= MFPA_EXP_ENV("MFPA_GEMM_PIPE_MINM", 192)) {   // (rows past M are clamped when loaded: a 249-row clip fills 97 % of a 256-row tile)
+  // 128-column tiles whenever the padded N allows them (precision 2 always does, see above)
+  const bool wide_ok = d->precision >= 1 && d->K % HKC == 0 && d->K >= 128 && d->npad % WBN == 0;
+  if (wide_ok && d->K % (2 * HKC) == 0 && d->M >= PIPE_MIN_M) {
     a.ny = (d->M + PBM - 1) / PBM;
     dim3 gw = grid1d(d->npad / WBN);
-    static const int persist = MFPA_EXP_ENV("MFPA_GEMM_PERSIST", 1);   // 0: one tile per workgroup (experiments)
     const unsigned cus8 = (unsigned)((mfpa_current_device_cus() + 7) / 8 * 8);
-    if (persist && cus8 >= 8 && gw.x > cus8) gw.x = cus8;    // persistent: one workgroup per CU walks the tiles (a multiple of 8: XCD ranges)
+    if (cus8 >= 8 && gw.x > cus8) gw.x = cus8;    // persistent: one workgroup per CU walks the tiles (a multiple of 8: XCD ranges)
     const size_t lds = (size_t)2 * (PBM + WBN) * HROW;
     if (d->precision == 2) hipLaunchKernelGGL(gemm_bf16x3_pipe_kernel<true>, gw, dim3(512), lds, st, a);
     else hipLaunchKernelGGL(gemm_bf16x3_pipe_kernel<false>, gw, dim3(512), lds, st, a);
-  } else if (d->precision == 2) {
+  } else if (wide_ok) {
     dim3 gw = grid1d(d->npad / WBN);
-    hipLaunchKernelGGL(gemm_bf16x3_wide_kernel<true>, gw, dim3(256), (size_t)2 * (GBM + WBN) * HROW, mfpa_stream(stream), a);
-  } else if (d->precision == 1 && d->K % HKC == 0 && d->K >= 128 && wide && d->npad % WBN == 0) {
-    dim3 gw = grid1d(d->npad / WBN);
-    hipLaunchKernelGGL(gemm_bf16x3_wide_kernel<false>, gw, dim3(256), (size_t)2 * (GBM + WBN) * HROW, mfpa_stream(stream), a);
+    const size_t lds = (size_t)2 * (GBM + WBN) * HROW;
+    if (d->precision == 2) hipLaunchKernelGGL(gemm_bf16x3_wide_kernel<true>, gw, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL(gemm_bf16x3_wide_kernel<false>, gw, dim3(256), lds, st, a);
   } else if (d->precision == 1 && d->K % HKC == 0 && d->K >= 128) {
     hipLaunchKernelGGL(gemm_bf16x3_kernel, grid, dim3(256), 0, mfpa_stream(stream), a);
-  } else if (d->precision == 1 && shortk && d->K == 48 && d->c1_x) {
+  } else if (d->precision == 1 && d->K == 48 && d->c1_x) {
     hipLaunchKernelGGL((gemm_shortk_bf16x3_kernel<true, 48, 48>), grid, dim3(256), SK_LDS(48) + 9 * 48 * 4, st, a);
-  } else if (d->precision == 1 && shortk && d->K == 48) {
+  } else if (d->precision == 1 && d->K == 48) {
     hipLaunchKernelGGL((gemm_shortk_bf16x3_kernel<false, 48, 48>), grid, dim3(256), SK_LDS(48), st, a);
-  } else if (d->precision == 1 && shortk && d->K == 96 && !d->c1_x) {
+  } else if (d->precision == 1 && d->K == 96 && !d->c1_x) {
     hipLaunchKernelGGL((gemm_shortk_bf16x3_kernel<false, 96, 48>), grid, dim3(256), SK_LDS(48), st, a);
   } else if (d->K == 48 && d->c1_x) {
     hipLaunchKernelGGL((gemm_smallk_kernel<true, 48>), grid, dim3(256), 0, mfpa_stream(stream), a);
   } else if (d->K == 48) {
     hipLaunchKernelGGL((gemm_smallk_kernel<false, 48>), grid, dim3(256), 0, mfpa_stream(stream), a);
-
   } else if (d->c1_x) {
     hipLaunchKernelGGL(gemm_mfma_kernel<true>, grid, dim3(256), 0, mfpa_stream(stream), a);
   } else {
@@ -1939,12 +1842,6 @@ int mfpa_conv1d_c1(const float* x, int B, int Lin, int Lout, int C, const float*
   hipLaunchKernelGGL(conv1d_c1_kernel, dim3((unsigned)blocks, B), dim3(256), 0, mfpa_stream(stream), x, Lin, Lout, C, w, bias, y, relu);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
-}
-
-int mfpa_conv1d_c1_relu(const float* x, int B, int Lin, int Lout, int C, const float* w, const float* bias, float* y,
-                        void* stream) {
-  if (B != 0 && !bias) return MFPA_EINVAL;
-  return mfpa_conv1d_c1(x, B, Lin, Lout, C, w, bias, 1, y, stream);
 }
 
 int mfpa_convT1d_c1(const float* P, int B, int L, int C, const float* w, float bias, float* y, void* stream) {
@@ -2009,11 +1906,6 @@ int mfpa_lstm_layer_range(const float* whh_grouped, float* xp, float* hseq, floa
   return MFPA_OK;
 }
 
-int mfpa_lstm_layer(const float* whh_grouped, float* xp, float* hseq, float* cseq, float* cstate, int B, int Tn, int H, float* xsum,
-                    const float* skip, int train, void* stream) {
-  return mfpa_lstm_layer_range(whh_grouped, xp, hseq, cseq, cstate, B, Tn, H, xsum, skip, train, 0, Tn, stream);
-}
-
 /* The persistent form of mfpa_lstm_layer_range (lstm_seq_kernel): one launch for steps [t0, t1).  `work` = device scratch of
  * mfpa_lstm_seq_work_bytes(B, H) bytes, private to this layer while the call is in flight; its error word (mfpa_lstm_seq_error)
  * must be zero before the first use (hipMemset the buffer once).  Shapes the persistent kernel does not take (H not 128 KS for
@@ -2028,8 +1920,7 @@ int mfpa_lstm_seq_error_offset(void) { return LSTM_ERR_WORD * 4; }
 
 int mfpa_lstm_seq_workgroups(int B, int H, int wg_budget, int* workgroups) {
   if (!workgroups || B < 0 || H < LKC || H % LKC) return MFPA_EINVAL;
-  static const int persistent = MFPA_EXP_ENV("MFPA_LSTM_SEQ", 1);
-  *workgroups = (persistent && B > 0) ? lstm_seq_plan(B, H, wg_budget, nullptr) : 0;
+  *workgroups = B > 0 ? lstm_seq_plan(B, H, wg_budget, nullptr) : 0;
   return MFPA_OK;
 }
 
@@ -2039,11 +1930,10 @@ int mfpa_lstm_layer_seq(const float* whh_grouped, float* xp, float* hseq, float*
   if (!whh_grouped || !xp || !hseq || !work || B < 0 || Tn < 0 || H < LKC || H % LKC || (xsum && !skip) || t0 < 0 || t1 > Tn) return MFPA_EINVAL;
   if (train ? !cseq : !cstate) return MFPA_EINVAL;
   const int ks = H / 128, ngroups = H / LU;
-  static const int persistent = MFPA_EXP_ENV("MFPA_LSTM_SEQ", 1);
   // every workgroup of the launch must be resident at once: the plan keeps them within `wg_budget` (0 = one per CU of the current
   // device; a caller running two such launches side by side -- the chunked two-stream pipeline -- passes half the CU count)
   int ms = 2;
-  const int wgs = persistent ? lstm_seq_plan(B, H, wg_budget, &ms) : 0;
+  const int wgs = lstm_seq_plan(B, H, wg_budget, &ms);
   if (wgs == 0)
     return mfpa_lstm_layer_range(whh_grouped, xp, hseq, cseq, cstate, B, Tn, H, xsum, skip, train, t0, t1, stream);
   const int nslab = (B + 32 * ms - 1) / (32 * ms);
@@ -2052,16 +1942,13 @@ int mfpa_lstm_layer_seq(const float* whh_grouped, float* xp, float* hseq, float*
   a.sync = reinterpret_cast<unsigned*>(work);
   a.hsplit = reinterpret_cast<char*>(work) + (size_t)LSTM_SYNC_WORDS * 4;
   a.B = B; a.Tn = Tn; a.H = H; a.t0 = t0; a.t1 = t1; a.train = train; a.nslab = nslab; a.ngroups = ngroups;
-  a.dbg = MFPA_EXP_ENV("MFPA_LSTM_DBG", 0);
   hipStream_t st = mfpa_stream(stream);
   MFPA_HIP(hipMemsetAsync(work, 0, (size_t)LSTM_ERR_WORD * 4, st));          // the slab counters; the error word stays
   const unsigned grid = (unsigned)(((nslab * ngroups + 7) / 8) * 8);
-  const size_t lds = (size_t)QW * 32 * ms * QGLD * sizeof(float) + (MFPA_LSTM_WIDE_PUT ? (size_t)32 * ms * 64 : 0);
-  static const int coh = MFPA_EXP_ENV("MFPA_LSTM_COH", 1);   // 0: one L1 / L2 invalidate per step + cached loads (7.83 vs 7.58 ms for both layers of 256 clips)
+  const size_t lds = (size_t)QW * 32 * ms * QGLD * sizeof(float) + (size_t)32 * ms * 64;
 #define SEQ_LAUNCH(KS_)                                                                                                   \
-  if (ms == 1) hipLaunchKernelGGL((lstm_seq_kernel<KS_, 1, 1>), dim3(grid), dim3(64 * QW), lds, st, a);                   \
-  else if (coh) hipLaunchKernelGGL((lstm_seq_kernel<KS_, 1, 2>), dim3(grid), dim3(64 * QW), lds, st, a);                  \
-  else hipLaunchKernelGGL((lstm_seq_kernel<KS_, 0, 2>), dim3(grid), dim3(64 * QW), lds, st, a)
+  if (ms == 1) hipLaunchKernelGGL((lstm_seq_kernel<KS_, 1>), dim3(grid), dim3(64 * QW), lds, st, a);                      \
+  else hipLaunchKernelGGL((lstm_seq_kernel<KS_, 2>), dim3(grid), dim3(64 * QW), lds, st, a)
   switch (ks) {
     case 2: SEQ_LAUNCH(2); break;
     case 4: SEQ_LAUNCH(4); break;
@@ -2098,17 +1985,8 @@ int mfpa_conv1d_c1_glu(const float* x, int B, int Lin, int Lout, int C, const fl
       (long long)Lout * C * 4 > 0xffffffffLL || Lin % 4 != 0 || ((size_t)x & 15) != 0)        // the rows' samples are read as aligned float4
     return MFPA_EINVAL;
   const int tiles = (Lout + 127) / 128;
-  hipLaunchKernelGGL(c1_glu_kernel, dim3((tiles + TT_TPW - 1) / TT_TPW, B), dim3(256), (size_t)MFPA_EXP_ENV("MFPA_HEAD_LDS", 0), mfpa_stream(stream), x, Lin, Lout, w1, b1, gw, gb, y,
+  hipLaunchKernelGGL(c1_glu_kernel, dim3((tiles + TT_TPW - 1) / TT_TPW, B), dim3(256), 0, mfpa_stream(stream), x, Lin, Lout, w1, b1, gw, gb, y,
                      tiles);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
-}
-int mfpa_lstm_cell(const float* gates, long long ldg, float* c, int B, int H, float* hout, long long ldh, float* hsum,
-                   const float* addend, long long ldadd, void* stream) {
-  if (B == 0) return MFPA_OK;
-  if (!gates || !c || !hout || B < 0 || H < 1 || (hsum && !addend)) return MFPA_EINVAL;
-  int gx = (B * H + 255) / 256; if (gx > 4096) gx = 4096;
-  hipLaunchKernelGGL(lstm_cell_kernel, dim3(gx), dim3(256), 0, mfpa_stream(stream), gates, ldg, c, B, H, hout, ldh, hsum, addend, ldadd);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
 }

@@ -11,7 +11,6 @@
 //   lstm_step_bwd_kernel  one backward time step: dh_rec = dgates[t+1] W_hh, then the cell backward, in one launch
 //   downsample2 adjoint, the two 1-channel convolutions' weight gradients, column sums (bias gradients)
 #include "mfpa_common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -33,7 +32,7 @@ struct TnArgs {
   float* colsum;               // optional: colsum[m] += sum over all rows of A[.][m] (the bias gradient), by the n-tile-0 workgroups
   int R, M, N;
   int rs, spb;                 // rows per split, splits per clip
-  int tiles, nsplit, xcd;      // 1-D launch: tiles x nsplit workgroups; xcd = 1: XCD-aware order
+  int tiles, nsplit;           // 1-D launch: tiles x nsplit workgroups
 };
 
 // (tile, split) of a workgroup.  Every tile of one K split reads the same rows of A and Bm; consecutive workgroup ids go round-robin
@@ -41,11 +40,8 @@ struct TnArgs {
 // of the (split, tile) order, tiles fastest: the tiles of a split run back to back on ONE XCD.
 __device__ __forceinline__ bool tn_tile(const TnArgs& a, int& tile, int& split) {
   const unsigned total = (unsigned)a.tiles * a.nsplit;
-  unsigned lin = blockIdx.x;
-  if (a.xcd) {
-    const unsigned per = (total + 7) / 8;
-    lin = (blockIdx.x % 8) * per + blockIdx.x / 8;
-  }
+  const unsigned per = (total + 7) / 8;
+  const unsigned lin = (blockIdx.x % 8) * per + blockIdx.x / 8;
   if (lin >= total) return false;
   tile = lin % a.tiles;
   split = lin / a.tiles;
@@ -497,10 +493,7 @@ constexpr int BKC = 128;
 constexpr int BROW = 4 * BKC + 16;       // LDS row bytes [128 hi | 128 lo | pad]
 constexpr int BU = 32;
 constexpr int BTHREADS = 512;
-#ifndef MFPA_LSTM_BPF
-#define MFPA_LSTM_BPF 6
-#endif
-constexpr int BPF = MFPA_LSTM_BPF;       // chunks of global loads in flight per thread
+constexpr int BPF = 6;                   // chunks of global loads in flight per thread
 
 // MT: 32-clip tiles per workgroup: 2 = (clip half) x (K quarter), 1 = K eighths (small batches: twice the workgroups).
 // BUT: hidden units per workgroup, 32 or 16 (16: the matrix tile is half empty, but the step is bound by the bytes a workgroup
@@ -883,13 +876,11 @@ static int lstm_bwd_seq_cus() { return mfpa_current_device_cus(); }
 // slab size (mtb x 16 clips) and resident workgroups of the persistent backward launch; 0 = the per-step path
 static int lstm_bwd_seq_plan(int B, int H, int wg_budget, int* mtb_out) {
   const int ks = (H % 64 == 0) ? H / 64 : 0, ngroups = H / 16;
-  static const int force_mtb = MFPA_EXP_ENV("MFPA_LSTM_BWD_MTB", 0);
   const int cus = lstm_bwd_seq_cus();
   const int budget = (wg_budget > 0 && wg_budget < cus) ? wg_budget : cus;
   int mtb = 0;
   for (int c = 1; c <= 4 && !mtb; c *= 2)
     if ((long long)((B + 16 * c - 1) / (16 * c)) * ngroups <= budget) mtb = c;
-  if (force_mtb == 1 || force_mtb == 2 || force_mtb == 4) mtb = force_mtb;
   const int nslab = mtb ? (B + 16 * mtb - 1) / (16 * mtb) : 0;
   if (mtb_out) *mtb_out = mtb;
   if (!mtb || !(ks == 4 || ks == 8 || ks == 12) || nslab > 32 || (long long)B * H * 32 > 0x7fffffffLL || (long long)nslab * ngroups > budget)
@@ -920,8 +911,7 @@ int mfpa_gemm_tn(const mfpa_gemm_tn_desc* d, void* stream) {
   TnArgs a{};
   a.A = d->A; a.lda = d->lda; a.strideA = d->strideA; a.Bm = d->Bm; a.ldb = d->ldb; a.strideB = d->strideB;
   a.C = d->C; a.ldc = d->ldc; a.colsum = d->colsum; a.R = d->R; a.M = d->M; a.N = d->N; a.rs = (int)rs; a.spb = (int)spb;
-  static const int xcd_env = MFPA_EXP_ENV("MFPA_GEMM_XCD", 1);
-  a.tiles = (int)tiles; a.nsplit = (int)(spb * d->batch); a.xcd = xcd_env;
+  a.tiles = (int)tiles; a.nsplit = (int)(spb * d->batch);
   if (tiles * a.nsplit > 0x3fffffffLL) return MFPA_EINVAL;
   dim3 grid((unsigned)(((tiles * a.nsplit + 7) / 8) * 8));
   hipStream_t st = mfpa_stream(stream);
@@ -997,12 +987,8 @@ int mfpa_lstm_step_bwd(const float* dgnext, long long ldgn, const float* whhT, f
   if (B == 0) return MFPA_OK;
   if (!whhT || !gates || !ct || !dhout || !dcstate || B < 0 || H < BKC || H % BKC) return MFPA_EINVAL;
   if (ldgn % 4 || ldg % 4 || ldct % 4 || ldcp % 4 || lddh % 4) return MFPA_EINVAL;
-  static const int force = MFPA_EXP_ENV("MFPA_LSTM_MT", 0);
-  static const int force_bu = MFPA_EXP_ENV("MFPA_LSTM_BU", 0);
-  int MT = ((long long)(H / BU) * ((B + 31) / 32) <= 256) ? 1 : 2;   // 32-clip tiles while they leave the chip under-filled
-  if (force == 1 || force == 2) MT = force;
-  int but = (MT == 1 && (long long)(H / 16) * ((B + 31) / 32) <= 128) ? 16 : 32;   // 16-unit groups while even those leave half the chip free
-  if (force_bu == 16 || force_bu == 32) but = (MT == 1) ? force_bu : 32;
+  const int MT = ((long long)(H / BU) * ((B + 31) / 32) <= 256) ? 1 : 2;   // 32-clip tiles while they leave the chip under-filled
+  const int but = (MT == 1 && (long long)(H / 16) * ((B + 31) / 32) <= 128) ? 16 : 32;   // 16-unit groups while even those leave half the chip free
   const int mtiles = (B + 32 * MT - 1) / (32 * MT);
   const long long total = (long long)(H / but) * mtiles;
   if (total > 0x7fffff) return MFPA_EINVAL;
@@ -1022,7 +1008,7 @@ int mfpa_lstm_step_bwd(const float* dgnext, long long ldgn, const float* whhT, f
 }
 
 /* The backward recurrence of a whole LSTM layer: mfpa_lstm_step_bwd for t = Tn-1 .. 0 from one host loop.  gates / cseq / dhout
- * are (B, Tn, .) as mfpa_lstm_layer(train = 1) left them; dcstate (B, H) scratch (zeroed here). */
+ * are (B, Tn, .) as mfpa_lstm_layer_range(train = 1) left them; dcstate (B, H) scratch (zeroed here). */
 int mfpa_lstm_layer_bwd_range(const float* whhT, float* gates, const float* cseq, const float* dhout, float* dcstate, int B, int Tn,
                               int H, int t0, int t1, void* stream) {
   if (B == 0 || Tn == 0 || t1 <= t0) return MFPA_OK;
@@ -1038,11 +1024,6 @@ int mfpa_lstm_layer_bwd_range(const float* whhT, float* gates, const float* cseq
   return MFPA_OK;
 }
 
-int mfpa_lstm_layer_bwd(const float* whhT, float* gates, const float* cseq, const float* dhout, float* dcstate, int B, int Tn, int H,
-                        void* stream) {
-  return mfpa_lstm_layer_bwd_range(whhT, gates, cseq, dhout, dcstate, B, Tn, H, 0, Tn, stream);
-}
-
 /* mfpa_lstm_layer_bwd_range as ONE persistent launch (lstm_bwd_seq_kernel): same arguments and results; `work` = device scratch of the
  * size mfpa_lstm_bwd_seq_work_bytes reports, owned by this layer while the call runs, zeroed once before its first use; the error
  * word (bounded waits, as for mfpa_lstm_layer_seq) sits at the same byte offset.  Shapes outside the persistent kernel's range
@@ -1056,8 +1037,7 @@ int mfpa_lstm_bwd_seq_work_bytes(int B, int H, long long* bytes) {
 
 int mfpa_lstm_bwd_seq_workgroups(int B, int H, int wg_budget, int* workgroups) {
   if (!workgroups || B < 0 || H < 64) return MFPA_EINVAL;
-  static const int persistent = MFPA_EXP_ENV("MFPA_LSTM_BWD_SEQ", 1);
-  *workgroups = (persistent && B > 0) ? lstm_bwd_seq_plan(B, H, wg_budget, nullptr) : 0;
+  *workgroups = B > 0 ? lstm_bwd_seq_plan(B, H, wg_budget, nullptr) : 0;
   return MFPA_OK;
 }
 
@@ -1066,12 +1046,10 @@ int mfpa_lstm_layer_bwd_seq(const float* whhT, float* gates, const float* cseq, 
   if (B == 0 || Tn == 0 || t1 <= t0) return MFPA_OK;
   if (!whhT || !gates || !cseq || !dhout || !dcstate || !work || B < 0 || Tn < 0 || t0 < 0 || t1 > Tn || H < 64) return MFPA_EINVAL;
   const int ks = (H % 64 == 0) ? H / 64 : 0, ngroups = H / 16;
-  static const int persistent = MFPA_EXP_ENV("MFPA_LSTM_BWD_SEQ", 1);
   // the smallest slab (16, 32 or 64 clips) whose workgroups still fit the chip: more CUs share the reading of dgates[t+1]
-  // (every workgroup of a launch must be resident at once; a caller that runs two such launches side by side -- the chunked
-  // two-stream pipeline -- passes half the CUs as wg_budget, 0 = all of them)
+  // (every workgroup of a launch must be resident at once: at most wg_budget of them, 0 = one per CU)
   int mtb = 0;
-  const int wgs = persistent ? lstm_bwd_seq_plan(B, H, wg_budget, &mtb) : 0;
+  const int wgs = lstm_bwd_seq_plan(B, H, wg_budget, &mtb);
   if (wgs == 0)
     return mfpa_lstm_layer_bwd_range(whhT, gates, cseq, dhout, dcstate, B, Tn, H, t0, t1, stream);
   const int nslab = (B + 16 * mtb - 1) / (16 * mtb);

@@ -33,13 +33,11 @@ def valid_length(length: int) -> int:
     return int(math.ceil(length / RESAMPLE))
 
 
-PAD_N_TO_WIDE_TILE = True   # K >= 128 layers with 128 < N, N % 128 != 0 (the two N = 192 layers): weight rows zero-padded to a multiple of
-                            # 128 so that the pipelined 256 x 128 tile serves them (a third of the second column tile is idle) instead of
-                            # the round-1 128 x 64 tile
-
-
 def _wide_mult(n: int, k: int) -> int:
-    return 128 if (PAD_N_TO_WIDE_TILE and n > 128 and n % 128 and k >= 128 and k % 64 == 0) else 64
+    """Row multiple of a packed weight: K >= 128 layers with 128 < N, N % 128 != 0 (the two N = 192 layers) are zero-padded to a
+    multiple of 128 so that the pipelined 256 x 128 tile serves them (a third of the second column tile is idle) instead of the
+    128 x 64 tile."""
+    return 128 if (n > 128 and n % 128 and k >= 128 and k % 64 == 0) else 64
 
 
 def _pad_rows(w: torch.Tensor, mult: int = 64) -> torch.Tensor:
@@ -88,14 +86,6 @@ def pack_demucs_weights(sd: Dict[str, torch.Tensor], device) -> Dict[str, torch.
         if d == DEPTH - 1:
             pw["decL.w"] = w[:, 0, :].t().contiguous()         # (8, h): rows j (current row taps 0..3) and j+4 (previous row)
             pw["decL.b"] = float(f(f"decoder.{d}.2.bias")[0])
-            # the same layer as a strided-window GEMM (row t = [g[t-1] | g[t]], K = 2h, N = 4 outputs, padded to one 64-row tile)
-            wg = torch.zeros((64, 2 * h), dtype=torch.float32, device=w.device)
-            wg[:4, :h] = w[:, 0, 4:8].t()
-            wg[:4, h:] = w[:, 0, 0:4].t()
-            pw["decL.wg"] = wg
-            bg = torch.zeros(64, dtype=torch.float32, device=w.device)
-            bg[:4] = f(f"decoder.{d}.2.bias")[0]
-            pw["decL.bg"] = bg
         else:
             # row n = j*cout + co, K = [previous row g[t-1] -> tap j+4 | current row g[t] -> tap j]
             wt = torch.cat([w[:, :, 4:8].permute(2, 1, 0), w[:, :, 0:4].permute(2, 1, 0)], dim=2)   # (4, cout, 2h)
@@ -121,13 +111,7 @@ def _p(t: torch.Tensor, off_floats: int = 0) -> int:
     return ptr(t) + 4 * off_floats
 
 
-FUSE_FIRST_LAYER = True   # False: run mfpa_conv1d_c1_relu as its own launch
-FUSE_FIRST_LEVEL = True   # False: the first convolution inside the loader of the 128 x 64-tile GLU GEMM (evaluated twice per row)
-_PAD_ROWS_ONLY = True   # zero only the two padding rows of the GLU output (0: memset the whole buffer)
-FUSE_LAST_LEVEL = True    # False: the last decoder level as two launches (1x1 + GLU, then the transposed convolution)
-LAST_LAYER_GEMM = True    # False: the stand-alone VALU kernel mfpa_convT1d_c1 for the last ConvTranspose1d
 PRESPLIT_WEIGHTS = True   # False: the GEMMs split the fp32 weights on the fly (the only form the training engine uses)
-SPLIT_MIN_ROWS = 1        # rows of A from which the pre-split operand (the 128 x 128 kernel) is used
 PRECISION = 1     # 0: exact fp32 products (v_mfma_f32_32x32x2_f32); 1: bf16x3 (3 bf16 MFMAs per product, fp32 accumulate)
 
 
@@ -156,7 +140,7 @@ def gemm(A: int, lda, strideA, batch, M, W, bias, N, C: int, ldc, strideC, *, mo
     wptr = ptr(W)
     if precision == 1 and c1 is None:
         ent = getattr(W, "_mfpa_split", None)
-        if ent is not None and ent[0] == W._version and M >= SPLIT_MIN_ROWS:
+        if ent is not None and ent[0] == W._version:
             wptr, precision = ptr(ent[1]), 2
     d = GemmDesc(A=A, lda=lda, strideA=strideA, W=wptr, bias=ptr(bias), addend=addend, ldadd=ldadd,
                  strideAdd=strideAdd, C=C, ldc=ldc, strideC=strideC, batch=batch, M=M, N=N, K=W.shape[1], npad=W.shape[0],
@@ -168,8 +152,6 @@ def gemm(A: int, lda, strideA, batch, M, W, bias, N, C: int, ldc, strideC, *, mo
         check(lib().mfpa_gemm_mfma(ctypes.byref(d), stream()), "mfpa_gemm_mfma")
 
 
-
-PIPELINE_LSTM = True      # False: the two LSTM layers one after the other on the current stream
 PIPELINE_MAX_CLIPS = 96   # above this a step fills the chip on its own: forward 7.1 -> 5.5 ms at 16 clips, 13.6 -> 12.6 at 64, 21.3 -> 22.0 at 128
 LSTM_CHUNK = 31   # time steps per pipeline stage (248 = 8 x 31)
 _SIDE_STREAMS: Dict[int, "torch.cuda.Stream"] = {}
@@ -184,9 +166,6 @@ def _side_stream(dev) -> "torch.cuda.Stream":
 
 PERSISTENT_LSTM = True    # False: one launch per time step (mfpa_lstm_layer_range)
 PERSISTENT_LSTM_BWD = True   # training: the backward recurrence as one launch per range too (mfpa_lstm_layer_bwd_seq)
-PIPELINE_LSTM_BWD = False    # training: the two layers' backward recurrences as a chunk pipeline on two streams, like the forward (measured at 64 clips,
-                             # ms per step, three runs each: persistent + one layer after the other 41.1 / 41.7 / 42.8; per-step launches + pipeline
-                             # 42.3 / 42.6 / 42.7; persistent + pipeline 43.2 / 43.5 / 45.6; per-step, no pipeline 44.1 / 44.3 / 45.4)
 _LSTM_WORK: Dict[tuple, list] = {}
 _LSTM_TOUCHED: Dict[int, list] = {}      # device index -> work-buffer entries used since the last lstm_results_ok()
 
@@ -340,9 +319,11 @@ def lstm_two_layers(x: torch.Tensor, skip: torch.Tensor, wih, bias, whh_grouped,
     """Both LSTM layers (model.py:91-110) on x (B, Tn, H): returns (xsum = h1 + skip, saved) with saved = per layer
     (input, gates-or-projections, hseq, cseq-or-None).
 
-    A time step of one layer occupies 48-96 of the 256 CUs (it is bound by what those CUs can stream), so the two
-    layers run as a PIPELINE on two streams: while layer 0 works on chunk k+1 of the sequence on the current stream, a side
-    stream projects chunk k of its output (h0 W_ih1^T) and runs layer 1 on it.  Joined before returning."""
+    A time step of one layer occupies 48-96 of the 256 CUs (it is bound by what those CUs can stream), so up to
+    PIPELINE_MAX_CLIPS clips the two layers run as a PIPELINE on two streams: while layer 0 works on chunk k+1 of the sequence on
+    the current stream, a side stream projects chunk k of its output (h0 W_ih1^T) and runs layer 1 on it.  Joined before returning.
+    Larger batches fill the chip with one layer, and sequences of at most LSTM_CHUNK steps have nothing to overlap: there the
+    layers run one after the other."""
     B, Tn, H = x.shape
     dev = x.device
     L = lib()
@@ -356,7 +337,7 @@ def lstm_two_layers(x: torch.Tensor, skip: torch.Tensor, wih, bias, whh_grouped,
         gemm(_p(x), H, 0, 1, B * Tn, wih[0], bias[0], 4 * H, _p(xp[0]), 4 * H, 0, precision=precision)
 
         work = [_lstm_work(dev, k, B, H) for k in range(2)] if PERSISTENT_LSTM else None
-        pipelined = PIPELINE_LSTM and Tn > LSTM_CHUNK and B <= PIPELINE_MAX_CLIPS
+        pipelined = Tn > LSTM_CHUNK and B <= PIPELINE_MAX_CLIPS
         # two persistent launches run side by side in the chunked pipeline: each may keep half the CUs' worth of workgroups resident
         wg_budget = torch.cuda.get_device_properties(dev).multi_processor_count // 2 if pipelined else 0
         wgs = lstm_seq_workgroups(B, H, wg_budget) if work is not None else 0
@@ -431,25 +412,21 @@ def _demucs_forward(pw: Dict[str, torch.Tensor], wav: torch.Tensor, precision: i
     for i in range(DEPTH):
         C = chans[i]
         Lout = (Lin - KERNEL) // STRIDE + 1
-        if i == 0 and FUSE_FIRST_LAYER:
-            # Conv1d(1 -> 48, k8, s4) + ReLU is evaluated inside the loader of the 1x1 + GLU GEMM: its (B, L, 48) output
-            # (12 MB per clip) is never written
+        if i == 0:
+            # Conv1d(1 -> 48, k8, s4) + ReLU is evaluated inside the 1x1 + GLU launch: its (B, L, 48) output (12 MB per clip) is
+            # never written
             h = new(B, Lout, C)
-            if FUSE_FIRST_LEVEL and precision == 1 and C == 48 and Lin % 4 == 0:   # one workgroup per 128 rows owns all packed GLU columns
+            if precision == 1 and C == 48 and Lin % 4 == 0:   # one workgroup per 128 rows owns all packed GLU columns
                 with timed():                # counted with the GEMM family (bench.py's roofline block)
                     check(L.mfpa_conv1d_c1_glu(ptr(x), B, Lin, Lout, C, ptr(pw["enc0.w"]), ptr(pw["enc0.b"]), ptr(pw["enc0.gw"]),
                                                ptr(pw["enc0.gb"]), ptr(h), stream()), "mfpa_conv1d_c1_glu")
-            else:
+            else:                            # precision 0: the first convolution inside the loader of the GLU GEMM
                 gemm_p(0, C, Lout * C, B, Lout, pw["enc0.gw"], pw["enc0.gb"], C, _p(h), C, Lout * C, mode=1,
                        c1=(x, pw["enc0.w"], pw["enc0.b"]))
         else:
             a = new(B, Lout, C)
-            if i == 0:
-                check(L.mfpa_conv1d_c1_relu(ptr(x), B, Lin, Lout, C, ptr(pw["enc0.w"]), ptr(pw["enc0.b"]), ptr(a), stream()),
-                      "mfpa_conv1d_c1_relu")
-            else:
-                Cin = chans[i - 1]                               # row t = h[4t : 4t+8] flattened: stride 4*Cin, K = 8*Cin
-                gemm_p(_p(h), STRIDE * Cin, Lin * Cin, B, Lout, pw[f"enc{i}.w"], pw[f"enc{i}.b"], C, _p(a), C, Lout * C, relu=1)
+            Cin = chans[i - 1]                                   # row t = h[4t : 4t+8] flattened: stride 4*Cin, K = 8*Cin
+            gemm_p(_p(h), STRIDE * Cin, Lin * Cin, B, Lout, pw[f"enc{i}.w"], pw[f"enc{i}.b"], C, _p(a), C, Lout * C, relu=1)
             h = new(B, Lout, C)
             gemm_p(_p(a), C, Lout * C, B, Lout, pw[f"enc{i}.gw"], pw[f"enc{i}.gb"], C, _p(h), C, Lout * C, mode=1)
         skips.append(h)
@@ -464,19 +441,17 @@ def _demucs_forward(pw: Dict[str, torch.Tensor], wav: torch.Tensor, precision: i
     Lcur = Tn
     for d in range(DEPTH):
         C = chans[DEPTH - 1 - d]
-        if d == DEPTH - 1 and FUSE_LAST_LEVEL and precision == 1 and C == 48:
-            y = new(B, 4 * (Lcur + 1))                           # 1x1 + GLU + ConvTranspose1d(48 -> 1) without the GLU output in memory
+        if d == DEPTH - 1 and precision == 1 and C == 48:
+            # 1x1 + GLU + ConvTranspose1d(48 -> 1) without the GLU output in memory; otherwise the two launches below
+            y = new(B, 4 * (Lcur + 1))
             with timed():
                 check(L.mfpa_glu_convT1d_c1(ptr(x), B, Lcur, C, ptr(pw[f"dec{d}.gw"]), ptr(pw[f"dec{d}.gb"]), ptr(pw["decL.w"]), pw["decL.b"],
                                             ptr(y), stream()), "mfpa_glu_convT1d_c1")
             x, Lcur = y, 4 * (Lcur + 1)
             break
-        if _PAD_ROWS_ONLY:
-            P = new(B, Lcur + 2, C)                                                # rows 0 and L+1 are the zero padding
-            P[:, 0].zero_()
-            P[:, Lcur + 1].zero_()
-        else:
-            P = torch.zeros((B, Lcur + 2, C), dtype=torch.float32, device=dev)      # rows 0 and L+1 stay zero
+        P = new(B, Lcur + 2, C)                                  # rows 0 and L+1 are the zero padding
+        P[:, 0].zero_()
+        P[:, Lcur + 1].zero_()
         gemm_p(_p(x), C, Lcur * C, B, Lcur, pw[f"dec{d}.gw"], pw[f"dec{d}.gb"], C, _p(P, C), C, (Lcur + 2) * C, mode=1)
         Lnext = 4 * (Lcur + 1)                                   # (L - 1) * 4 + 8
         if d < DEPTH - 1:
@@ -485,11 +460,6 @@ def _demucs_forward(pw: Dict[str, torch.Tensor], wav: torch.Tensor, precision: i
             y = new(B, Lnext, cout)                              # row t = [g[t-1] | g[t]] -> positions 4t .. 4t+3
             gemm_p(_p(P), C, (Lcur + 2) * C, B, Lcur + 1, pw[f"dec{d}.w"], pw[f"dec{d}.b"], 4 * cout, _p(y), 4 * cout,
                  Lnext * cout, mode=2, relu=2, addend=_p(skip), ldadd=4 * cout, strideAdd=Lnext * cout)
-        elif LAST_LAYER_GEMM and precision == 1:
-            # ConvTranspose1d(48 -> 1) as the same strided-window GEMM (K = 96, four output columns): the VALU kernel reads every
-            # row of P eight times (2.2 ms per 256 clips), the short-K bf16x3 GEMM streams it once (1.2 ms)
-            y = new(B, Lnext)
-            gemm_p(_p(P), C, (Lcur + 2) * C, B, Lcur + 1, pw["decL.wg"], pw["decL.bg"], 4, _p(y), 4, Lnext)
         else:
             y = new(B, Lnext)
             check(L.mfpa_convT1d_c1(ptr(P), B, Lcur, C, ptr(pw["decL.w"]), pw["decL.b"], ptr(y), stream()), "mfpa_convT1d_c1")

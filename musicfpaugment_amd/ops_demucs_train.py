@@ -99,8 +99,6 @@ class _Phase:
 
 def _padded(new, zeros, B: int, L: int, C: int) -> torch.Tensor:
     """(B, L + 2, C) buffer whose rows 0 and L + 1 are zero; the L rows between are written by the GEMM that follows."""
-    if not D._PAD_ROWS_ONLY:
-        return zeros(B, L + 2, C)
     t = new(B, L + 2, C)
     t[:, 0].zero_()
     t[:, L + 1].zero_()
@@ -440,44 +438,25 @@ class DemucsTrainEngine:
         (seq0, g0, hseq0, cseq0), (seq1, g1, hseq1, cseq1) = S["lstm"]
         dc0, dc1, dx1 = new(B, H), new(B, H), new(B, Tn, H)
         with timed():
-            pipelined = D.PIPELINE_LSTM and D.PIPELINE_LSTM_BWD and Tn > D.LSTM_CHUNK and B <= D.PIPELINE_MAX_CLIPS
-            # two persistent launches run side by side in the chunked pipeline: each may keep half the CUs' worth of workgroups resident
-            wg_budget = torch.cuda.get_device_properties(dev).multi_processor_count // 2 if pipelined else 0
             bwork = {id(g1): D._lstm_work(dev, 1, B, H, backward=True), id(g0): D._lstm_work(dev, 0, B, H, backward=True)} if D.PERSISTENT_LSTM_BWD else None
 
-            bwgs = D.lstm_seq_workgroups(B, H, wg_budget, backward=True) if bwork is not None else 0
+            bwgs = D.lstm_seq_workgroups(B, H, 0, backward=True) if bwork is not None else 0
 
-            def bwd(whhT, gates, cseq, dhout, dc, a, b):
-                if bwork is not None:            # one persistent launch for the range (csrc/demucs_train.hip: lstm_bwd_seq_kernel)
+            def bwd(whhT, gates, cseq, dhout, dc):
+                if bwork is not None:            # one persistent launch for the layer (csrc/demucs_train.hip: lstm_bwd_seq_kernel)
                     done = D._GUARD.admit(dev, bwgs)
-                    check(L.mfpa_lstm_layer_bwd_seq(ptr(whhT), ptr(gates), ptr(cseq), ptr(dhout), ptr(dc), B, Tn, H, a, b, wg_budget,
+                    check(L.mfpa_lstm_layer_bwd_seq(ptr(whhT), ptr(gates), ptr(cseq), ptr(dhout), ptr(dc), B, Tn, H, 0, Tn, 0,
                                                     ptr(bwork[id(gates)]), stream()), "mfpa_lstm_layer_bwd_seq")
                     done()
                     return
-                check(L.mfpa_lstm_layer_bwd_range(ptr(whhT), ptr(gates), ptr(cseq), ptr(dhout), ptr(dc), B, Tn, H, a, b, stream()),
+                check(L.mfpa_lstm_layer_bwd_range(ptr(whhT), ptr(gates), ptr(cseq), ptr(dhout), ptr(dc), B, Tn, H, 0, Tn, stream()),
                       "mfpa_lstm_layer_bwd_range")
 
-            def dx_chunk(a, b):                                              # dL/d(h0)[:, a:b] = dgates1[:, a:b] W_ih1
-                D.gemm(_p(g1, a * 4 * H), 4 * H, Tn * 4 * H, B, b - a, W["lstm1.wihT"], None, H, _p(dx1, a * H), H, Tn * H, precision=prec)
-
-            if not pipelined:
-                bwd(W["lstm1.whhT"], g1, cseq1, dxsum, dc1, 0, Tn)
-                dx_chunk(0, Tn)
-                bwd(W["lstm0.whhT"], g0, cseq0, dx1, dc0, 0, Tn)
-            else:       # layer 1 runs backwards through the chunks on this stream, layer 0 follows one chunk behind on the side stream
-                main, side = torch.cuda.current_stream(dev), D._side_stream(dev)
-                side.wait_stream(main)
-                starts = list(range(0, Tn, D.LSTM_CHUNK))
-                for a in reversed(starts):
-                    b = min(Tn, a + D.LSTM_CHUNK)
-                    bwd(W["lstm1.whhT"], g1, cseq1, dxsum, dc1, a, b)
-                    ev = torch.cuda.Event()
-                    ev.record(main)
-                    with torch.cuda.stream(side):
-                        side.wait_event(ev)
-                        dx_chunk(a, b)
-                        bwd(W["lstm0.whhT"], g0, cseq0, dx1, dc0, a, b)
-                main.wait_stream(side)
+            # the two layers one after the other (a two-stream chunk pipeline like the forward's measured slower here)
+            bwd(W["lstm1.whhT"], g1, cseq1, dxsum, dc1)
+            # dL/d(h0) = dgates1 W_ih1
+            D.gemm(_p(g1), 4 * H, Tn * 4 * H, B, Tn, W["lstm1.wihT"], None, H, _p(dx1), H, Tn * H, precision=prec)
+            bwd(W["lstm0.whhT"], g0, cseq0, dx1, dc0)
         if bwork is not None:
             D.lstm_mark(dev)                 # the error words of this step's persistent launches, copied right behind the recurrence
         for layer, (seq, gates, hseq) in enumerate(((seq0, g0, hseq0), (seq1, g1, hseq1))):

@@ -35,7 +35,7 @@ def test_derived_operands_match_the_inference_packing():
     W = eng._derive()
     pw = D.pack_demucs_weights(sd, "cpu")
     def same_rows(train, packed):
-        # the inference packing may append zero rows (ops_demucs.PAD_N_TO_WIDE_TILE: N padded to the wide GEMM tile); the rows that
+        # the inference packing may append zero rows (ops_demucs._wide_mult: N padded to the wide GEMM tile); the rows that
         # carry weights are the training operand's, bit for bit
         n = train.shape[0]
         return packed.shape[0] >= n and torch.equal(train, packed[:n]) and not packed[n:].any()

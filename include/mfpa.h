@@ -592,7 +592,9 @@ typedef struct mfpa_pack_job {
 } mfpa_pack_job;
 int mfpa_pack_conv_weights_batch(const mfpa_pack_job* jobs_dev, int njobs, long long total_tiles, void* stream);
 /* torch.optim.Adam step (train.py:661: lr 1e-3, betas (0.9, 0.999), eps 1e-8, no weight decay) on flat
- * arrays; g is multiplied by grad_scale first (1/world_size after a SUM all-reduce). step >= 1. */
+ * arrays; g is multiplied by grad_scale first (1/world_size after a SUM all-reduce). step >= 1.
+ * The hyper-parameters are taken as float32; the bias corrections 1 - beta^step are formed in double from
+ * those float32 betas (tests/test_gpu_adam.py). */
 int mfpa_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
                    float beta2, float eps, int step, float grad_scale, void* stream);
 

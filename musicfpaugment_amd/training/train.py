@@ -412,6 +412,8 @@ class Trainer:
         if len(g["params"]) != len(names):
             raise ValueError(f"optimizer state for {len(g['params'])} parameters, the model has {len(names)}")
         self.engine.lr = float(g["lr"])
+        # the whole param group, as torch.optim.Adam.load_state_dict restores it: a run built with other betas resumes with them
+        self.engine.betas, self.engine.eps = tuple(float(b) for b in g["betas"]), float(g["eps"])
         st = opt["state"]
         if len(st) == 0:                                         # saved before the first step
             self.engine.flat_m.zero_(); self.engine.flat_v.zero_(); self.engine.step_count = 0

@@ -1,5 +1,5 @@
 """Worker for tests/test_gpu_dist.py: one data-parallel Demucs train step per rank (both ranks on cuda:0, gloo backend so that two
-processes can share one GPU).  Rank r trains on clips [2r, 2r+2) of a 4-clip batch and dumps its gradients and parameters."""
+processes can share one GPU).  Rank r trains on clips [2r, 2r+2) of a 4-clip batch and dumps its gradients, parameters and Adam moments."""
 import os
 import sys
 
@@ -25,7 +25,7 @@ def main():
     loss = eng.train_step(torch.from_numpy(clean[lo:hi]).cuda(), torch.from_numpy(aug[lo:hi]).cuda())
     torch.cuda.synchronize()
     np.savez(os.path.join(out_dir, f"rank{rank}.npz"), params=eng.flat_p.cpu().numpy(), grads=eng.flat_g.cpu().numpy(),
-             loss=float(loss))
+             loss=float(loss), flat_m=eng.flat_m.cpu().numpy(), flat_v=eng.flat_v.cpu().numpy())
     dist.barrier()
     dist.destroy_process_group()
 

@@ -1,5 +1,6 @@
 """Worker for tests/test_gpu_dist.py: one data-parallel UNet train step per rank (both ranks on cuda:0, gloo backend so that two
-processes can share one GPU).  Rank r trains on clips [2r, 2r+2) of a 4-clip batch and dumps its updated flat parameters."""
+processes can share one GPU).  Rank r trains on clips [2r, 2r+2) of a 4-clip batch and dumps its updated flat parameters, the
+all-reduced gradient sum (the Adam launch only reads it, so it is still there after the step) and both Adam moments."""
 import os
 import sys
 
@@ -33,7 +34,8 @@ def main():
     loss = eng.train_step(am, ga.expand(hi - lo).contiguous(), target)
     torch.cuda.synchronize()
     np.savez(os.path.join(out_dir, f"rank{rank}.npz"), params=eng.flat_p.cpu().numpy(), loss=float(loss),
-             gmax=np.array([float(gc), float(ga)]))
+             gmax=np.array([float(gc), float(ga)]), flat_g=eng.flat_g.cpu().numpy(), flat_m=eng.flat_m.cpu().numpy(),
+             flat_v=eng.flat_v.cpu().numpy())
     dist.barrier()
     dist.destroy_process_group()
 

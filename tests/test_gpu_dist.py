@@ -1,6 +1,8 @@
 """The data-parallel training path on real GPU kernels with TWO processes: both ranks share cuda:0 and talk over gloo (RCCL needs
 one GPU per rank; the single-GPU test box has one).  Checks the scalar MAX all-reduce of the spectrogram maximum, the bucketed
-gradient all-reduce and the 1/world scaling inside the fused Adam step against an in-process emulation of the two ranks."""
+gradient all-reduce and the 1/world scaling inside the fused Adam step against an in-process emulation of the two ranks.  Adam's
+parameter update is invariant to a constant gradient scale, so the 1/world factor is read off the MOMENTS the ranks dump: dropped,
+exp_avg comes out 2x and exp_avg_sq 4x too large (relative L1 1.0 and 3.0)."""
 import os
 import subprocess
 import sys
@@ -55,6 +57,68 @@ def _check(r):
     raise AssertionError(tail)
 
 
+def _rel_l1(got, want):
+    want = np.asarray(want, dtype=np.float64)
+    return float(np.abs(np.asarray(got, dtype=np.float64) - want).sum() / np.abs(want).sum())
+
+
+def _check_moments_against_emulation(got, want_m, want_v, again_m, want_g=None):
+    """The two ranks' Adam moments after one data-parallel step against the emulation's (one Adam step at world 1 on the AVERAGED
+    gradient).  The only legitimate difference is float-atomic summation noise in the gradients, which reaches exp_avg linearly and
+    exp_avg_sq at twice the relative size.  It is measured, not assumed: `again_m` is exp_avg of a SECOND in-process run of the same
+    emulation, and the relative L1 between the two runs is the noise (floored at one float32 rounding, 2^-24, should two runs ever
+    agree to the bit).  Bounds: 10x the noise for exp_avg (and the gradient sum), 20x for exp_avg_sq; whatever the measurement
+    says, both must stay below 0.1 -- a dropped 1/2 shows as 1.0 on exp_avg and 3.0 on exp_avg_sq.
+    Measured on the MI355X: noise 7.6e-8 (UNet) / 7.5e-8 (Demucs); two ranks against the emulation 7.8e-8 / 8.1e-8 on exp_avg
+    and 1.8e-7 / 1.7e-7 on exp_avg_sq, so the bounds in force are about 7.5e-7 and 1.5e-6."""
+    for key in ("flat_m", "flat_v"):
+        np.testing.assert_array_equal(got[0][key], got[1][key])               # the replicas hold the same optimiser state
+    noise = max(_rel_l1(again_m, want_m), 2.0 ** -24)
+    bound_m, bound_v = 10 * noise, 20 * noise
+    assert bound_m < 0.1 and bound_v < 0.1, (noise, bound_m, bound_v)
+    dm, dv = _rel_l1(got[0]["flat_m"], want_m), _rel_l1(got[0]["flat_v"], want_v)
+    print(f"run-to-run noise of the emulation (relative L1 of exp_avg) {noise:.3e}; two ranks vs emulation: exp_avg {dm:.3e}, exp_avg_sq {dv:.3e}")
+    assert dm <= bound_m, f"exp_avg: relative L1 {dm:.3e} to the emulation, measured run-to-run noise {noise:.3e}, bound {bound_m:.3e}"
+    assert dv <= bound_v, f"exp_avg_sq: relative L1 {dv:.3e} to the emulation, measured run-to-run noise {noise:.3e}, bound {bound_v:.3e}"
+    if want_g is not None:
+        dg = _rel_l1(got[0]["flat_g"], want_g)
+        assert dg <= bound_m, f"summed gradient: relative L1 {dg:.3e} to the emulation, measured run-to-run noise {noise:.3e}, bound {bound_m:.3e}"
+
+
+def _emulated_unet_exp_avg(am, ga, target):
+    """exp_avg of the emulated two-rank UNet step, run once more (the run-to-run noise of the emulation itself)."""
+    from musicfpaugment_amd.ops_train import UNetTrainEngine
+    from musicfpaugment_amd.training.unet import UNet
+    grads, e0 = [], None
+    for k in range(2):
+        net = UNet(1, 1, rate=0.0)
+        net.load_state_dict(formula_state_dict(0))
+        eng = UNetTrainEngine(net.cuda().train(), lr=1e-3, precision=0)
+        pred = eng.forward(spec64=am[2 * k:2 * k + 2].contiguous(), denom=ga.expand(2).contiguous())
+        _, dpred = eng.l1_loss(pred, target[2 * k:2 * k + 2].contiguous())
+        eng.backward(dpred)
+        grads.append(eng.flat_g.clone())
+        e0 = eng if e0 is None else e0
+    e0.flat_g.copy_((grads[0] + grads[1]) / 2)
+    e0.optimizer_step()
+    return e0.flat_m.cpu().numpy()
+
+
+def _emulated_demucs_exp_avg(clean, aug):
+    from musicfpaugment_amd.ops_demucs_train import DemucsTrainEngine
+    from musicfpaugment_amd.training.demucs_weights import formula_state_dict as demucs_formula
+    gsum = None
+    for k in range(2):
+        eng = DemucsTrainEngine(demucs_formula(0), "cuda", lr=1e-3, precision=0)
+        pred = eng.forward(torch.from_numpy(aug[2 * k:2 * k + 2]).cuda())
+        _, _, _, dpred = eng.loss_and_grad(pred, torch.from_numpy(clean[2 * k:2 * k + 2]).cuda())
+        eng.backward(dpred)
+        gsum = eng.flat_g.clone() if gsum is None else gsum + eng.flat_g
+    eng.flat_g.copy_(gsum / 2)
+    eng.adam_step()
+    return eng.flat_m.cpu().numpy()
+
+
 def test_two_rank_train_step_matches_the_emulated_data_parallel_step():
     from musicfpaugment_amd import ops
     from musicfpaugment_amd.ops_train import UNetTrainEngine
@@ -95,6 +159,10 @@ def test_two_rank_train_step_matches_the_emulated_data_parallel_step():
     assert np.quantile(diff, 0.999) <= 1e-6, np.quantile(diff, 0.999)
     assert diff.max() <= 2.1e-3, diff.max()
     assert float(np.mean(diff > 1e-5)) < 1e-4
+    # the 1/world factor: the ranks' moments against the emulation's (e0 stepped at world 1 on the averaged gradient)
+    np.testing.assert_array_equal(got[0]["flat_g"], got[1]["flat_g"])
+    _check_moments_against_emulation(got, e0.flat_m.cpu().numpy(), e0.flat_v.cpu().numpy(), _emulated_unet_exp_avg(am, ga, target),
+                                     want_g=(grads[0] + grads[1]).cpu().numpy())
 
 
 def test_two_rank_peak_metrics_experiment_equals_single_process():
@@ -260,3 +328,7 @@ def test_two_rank_demucs_train_step():
     p0 = eng.flat_p.cpu().numpy()                                                # untouched initial parameters
     big = np.abs(g) > 1e-5
     np.testing.assert_allclose((got[0]["params"] - p0)[big], -1e-3 * np.sign(g[big]), atol=2e-5)
+    # the 1/world factor: one Adam step at world 1 on the AVERAGED gradient, and the ranks' moments against its moments
+    eng.flat_g.copy_(gsum / 2)
+    eng.adam_step()
+    _check_moments_against_emulation(got, eng.flat_m.cpu().numpy(), eng.flat_v.cpu().numpy(), _emulated_demucs_exp_avg(clean, aug))

@@ -36,11 +36,22 @@ extern "C" {
 #define MFPA_F32 0
 #define MFPA_F64 1
 
+/* The logarithm of the pickers' FLOAT32 (denoised) branch.  The reference takes np.log of a float32 array there
+ * (afp/audfprint/peak_extractor.py:265-276, afp/dejavu/fingerprint.py:70-79), and numpy's float32 log is a SIMD kernel that is
+ * not correctly rounded: it differs from the float64 log rounded once to float32 on 22 % of the float32 arguments in (1e-6, 1].
+ *   ROUNDED (the default): the float64 log rounded once to float32;
+ *   NUMPY: numpy's own float32 log restated (csrc/mfpa_nplog.h), equal to np.log on every non-negative float32 where numpy
+ *          dispatches that kernel (AVX512F or AVX2 + FMA3) -- the reference's log values bit for bit.
+ * MFPA_LOG_NUMPY_F32 is the bit of mfpa_audfprint_prepare's log_input that selects NUMPY. */
+#define MFPA_F32LOG_ROUNDED 0
+#define MFPA_F32LOG_NUMPY 1
+#define MFPA_LOG_NUMPY_F32 4
+
 #define MFPA_N_FFT 512
 #define MFPA_N_HOP 256
 #define MFPA_N_BINS 257
 
-/* ABI version: bumps when a signature changes. */
+/* ABI version: bumps when a signature changes or an entry point is added. */
 int mfpa_version(void);
 
 /* ---------------------------------------------------------------------------------------
@@ -106,7 +117,10 @@ int mfpa_f64_to_f32(const double* in, float* out, long long n, void* stream);
  *              (strict mode: everything downstream is IEEE add/mul/compare -> bit-exact);
  *              bit 1 (value 2): denom[b] is the maximum of the float64 spec[b] itself, as
  *              mfpa_stft_mag returned it with this spectrogram: max(spec / denom) is then 1
- *              exactly (NaN for an all-zero clip, like numpy) and the max pass is skipped
+ *              exactly (NaN for an all-zero clip, like numpy) and the max pass is skipped;
+ *              bit 2 (value 4, MFPA_LOG_NUMPY_F32): the log of a float32 spectrogram is numpy's own float32 log, np.log of the
+ *              UNet output at peak_extractor.py:265-276 bit for bit, instead of the float64 log rounded once to float32;
+ *              MFPA_EINVAL with dtype MFPA_F64 or together with bit 0 (there is no float32 log to take)
  *   filtered   (B, T, F-1) float64, FRAME-major workspace consumed by mfpa_audfprint_prune
  *   scratch    (B, F*T) float64 workspace
  */
@@ -156,6 +170,15 @@ int mfpa_dejavu_prepare(const double* psd, int B, int F, int T, const double* de
  * float32 array (the network output is C-contiguous: mean_order = 0); arr is that float32 result widened to float64. */
 int mfpa_dejavu_prepare_f32(const float* x, int B, int F, int T, int square, double scale, int mean_order, double* arr,
                             void* stream);
+/* The same with the float32 logarithm chosen: float32_log = MFPA_F32LOG_ROUNDED (what mfpa_dejavu_prepare_f32 computes) or
+ * MFPA_F32LOG_NUMPY (numpy's own float32 log: 10 * np.log(...) of fingerprint.py:78 on the float32 array of :70-75, bit for bit);
+ * any other value: MFPA_EINVAL. */
+int mfpa_dejavu_prepare_f32_ex(const float* x, int B, int F, int T, int square, double scale, int mean_order, int float32_log,
+                               double* arr, void* stream);
+/* y[i] = np.log(x[i]) as numpy's float32 SIMD kernel returns it (csrc/mfpa_nplog.h; the log the reference takes at
+ * afp/audfprint/peak_extractor.py:276 and afp/dejavu/fingerprint.py:78 after the UNet), x and y (n) float32, distinct arrays: MFPA_EINVAL when the two ranges overlap.
+ * x < 0 and NaN give NaN, 0 gives -inf, +inf gives +inf; denormals are handled whatever the denormal mode. */
+int mfpa_nplog_f32(const float* x, float* y, long long n, void* stream);
 int mfpa_localmax2d(const double* arr, int B, int F, int T, int radius, double amp_min,
                     uint8_t* mask, int32_t* npeaks, void* stream);
 

@@ -21,7 +21,7 @@ EINVAL = -22
 EHIP = -1000
 F32, F64 = 0, 1
 STFT_TABLE_LEN = 1288
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 
 class MfpaError(RuntimeError):
@@ -47,6 +47,8 @@ _SIGNATURES = {
                              c_void_p, c_void_p], c_int),
     "mfpa_dejavu_prepare": ([c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_int, c_void_p, c_void_p], c_int),
     "mfpa_dejavu_prepare_f32": ([c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p], c_int),
+    "mfpa_dejavu_prepare_f32_ex": ([c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_void_p], c_int),
+    "mfpa_nplog_f32": ([c_void_p, c_void_p, c_longlong, c_void_p], c_int),
     "mfpa_localmax2d": ([c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_dejavu_pick_work_doubles": ([c_int, c_int, c_void_p], c_int),
     "mfpa_dejavu_pick": ([c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,

@@ -32,7 +32,12 @@ def landmarks2hashes(landmarks_list) -> np.ndarray:
 
 class Audfprint_peaks(object):
     def __init__(self, params: Optional[Dict[str, Any]] = None, denoising: bool = False, denoising_model=None,
-                 unet=None, device="cuda", demucs=None) -> None:
+                 unet=None, device="cuda", demucs=None, float32_log: str = "rounded") -> None:
+        """`float32_log` ("rounded" | "numpy"): the logarithm find_peaks takes of the UNet's float32 output (:265-276) -- "numpy" is
+        numpy's own float32 log bit for bit, the reference's arithmetic; "rounded" (the default) the float64 log rounded once to
+        float32.  The un-denoised branch is float64 in the reference and is not affected."""
+        ops._float32_log_code(float32_log)
+        self.float32_log = float32_log
         params = afp_settings["audfprint"] if params is None else params
         self.density = params["density"]
         self.target_sr = params["samplerate"]
@@ -76,7 +81,8 @@ class Audfprint_peaks(object):
         a_dec = ops.audfprint_a_dec(self.density, self.n_hop)
         if self.unet is not None:
             spec = self.unet.denoise_spectrogram(mag, cmax, per_clip=True)        # float32 (B,257,nF)
-            filtered = ops.audfprint_prepare(spec, None, mean_order=0)            # C-contiguous in the reference
+            filtered = ops.audfprint_prepare(spec, None, mean_order=0,            # C-contiguous in the reference
+                                             float32_log=self.float32_log)
         elif want_spec:
             spec = ops.normalize_(mag, cmax, per_clip=True)
             filtered = ops.audfprint_prepare(spec, None, mean_order=1)            # |stft| is a transposed view there

@@ -35,13 +35,15 @@ def set_denoisers(unet=None, demucs=None) -> None:
 def fingerprint(channel_samples, Fs: float = afp_settings["dejavu"]["samplerate"], wsize: int = afp_settings["dejavu"]["n_fft"],
                 n_hop: int = afp_settings["dejavu"]["n_hop"], fan_value: int = afp_settings["dejavu"]["fan_value"],
                 amp_min: int = afp_settings["dejavu"]["amp_min"], denoising: bool = False, denoising_model: str = "unet",
-                get_masks: bool = "False", *, unet=None, device="cuda"):
+                get_masks: bool = "False", *, unet=None, device="cuda", float32_log: str = "rounded"):
     """afp/dejavu/fingerprint.py:34-91 for ONE clip, same signature and return forms: the list [(sha1 hex[:20], t1)] of hashes, or
     `(hashes, peak_mask (257, nF) float64, specgram (257, nF))` when `get_masks is True` -- the default is the STRING "False" and
     the test is `is True`, as in the reference (:43,88).  `channel_samples` are the raw (x 32767) samples Dejavu passes in.
     `denoising=True, denoising_model="unet"`: the spectrogram denoiser on the max-normalised PSD, output squared (:68-75), module
     from `unet=` or set_denoisers(); with "demucs" nothing happens HERE, as in the reference -- Dejavu denoises the waveform
-    before it calls fingerprint (dejavu.py:85-106).  Everything runs on the device (fingerprint_batch with a batch of one)."""
+    before it calls fingerprint (dejavu.py:85-106).  Everything runs on the device (fingerprint_batch with a batch of one).
+    `float32_log`: the logarithm of the UNet branch, as for fingerprint_peaks_batch."""
+    ops._float32_log_code(float32_log)
     if denoising:
         assert denoising_model in ["unet", "demucs"]
     if (int(wsize), int(n_hop)) != (ops.N_FFT, ops.N_HOP):
@@ -61,7 +63,8 @@ def fingerprint(channel_samples, Fs: float = afp_settings["dejavu"]["samplerate"
     cap = max(16, min(peaks, 16384) * max(int(fan_value) - 1, 1))      # more hashes can never come out under the kernel's peak limit
     dig, t1, counts, mask, spec = fingerprint_batch(x, amp_min=amp_min, fan_value=fan_value, cap=cap, scale_in=1.0,
                                                     peak_cap=min(peaks, 16384),
-                                                    denoising=net is not None, denoising_model="unet", unet=net)
+                                                    denoising=net is not None, denoising_model="unet", unet=net,
+                                                    float32_log=float32_log)
     n = int(counts[0])
     if n < 0:
         raise ValueError("more than 16384 peaks in one recording: outside the device kernel's limit (split the recording)")
@@ -85,7 +88,7 @@ def get_2D_peaks(arr2D, plot: bool = False, amp_min: int = afp_settings["dejavu"
 
 def fingerprint_peaks_batch(wav: torch.Tensor, amp_min: float = afp_settings["dejavu"]["amp_min"],
                             scale_in: float = 32767.0, denoising: bool = False, denoising_model: str = "unet",
-                            unet=None, demucs=None, want_spec: bool = True):
+                            unet=None, demucs=None, want_spec: bool = True, float32_log: str = "rounded"):
     """(B, T) float32 on the GPU -> (mask (B,257,nF) uint8, npeaks (B,), specgram (B,257,nF); None with want_spec=False on the
     un-denoised path, whose normalised specgram is one more pass over the PSD that the peaks do not need).
 
@@ -93,7 +96,10 @@ def fingerprint_peaks_batch(wav: torch.Tensor, amp_min: float = afp_settings["de
     denoiser on the max-normalised PSD (cast to float32), squares its output and keeps float32 for the log / mean steps
     (specgram is then float32); "demucs" denoises the waveform before the x 32767 scaling, the rest is the float64 path.
     The networks are passed in (``unet`` = training.unet.UNet in eval mode, ``demucs`` = training.model.Demucs); the
-    reference builds them at import time from checkpoint files."""
+    reference builds them at import time from checkpoint files.  ``float32_log`` ("rounded" | "numpy"): the logarithm taken of
+    the squared UNet output (fingerprint.py:78) -- "numpy" is numpy's own float32 log bit for bit, the reference's arithmetic;
+    "rounded" (the default) the float64 log rounded once to float32.  The float64 branches are not affected."""
+    ops._float32_log_code(float32_log)
     if denoising:
         if denoising_model not in ("unet", "demucs"):
             raise AssertionError("denoising_model must be 'unet' or 'demucs'")
@@ -105,7 +111,7 @@ def fingerprint_peaks_batch(wav: torch.Tensor, amp_min: float = afp_settings["de
     psd, cmax = ops.specgram_psd(wav, scale_in=scale_in)
     if denoising and denoising_model == "unet":
         y = unet.denoise_spectrogram(psd, cmax, per_clip=True)               # (B, 257, nF) float32
-        arr = ops.dejavu_prepare_f32(y, square=True, scale=10.0, mean_order=0)
+        arr = ops.dejavu_prepare_f32(y, square=True, scale=10.0, mean_order=0, float32_log=float32_log)
         mask, npeaks = ops.localmax2d(arr, PEAK_NEIGHBORHOOD_SIZE, float(amp_min))
         return mask, npeaks, y * y
     F, T = psd.shape[1:]
@@ -143,7 +149,7 @@ def fingerprint_batch(wav: torch.Tensor, amp_min: float = afp_settings["dejavu"]
                       peak_cap: int = None, **denoise):
     """fingerprint(...) for a batch (afp/dejavu/fingerprint.py:34-91): (digests (B,cap,10) uint8, t1 (B,cap), counts (B,),
     peak mask, normalised specgram), everything on the device.  ``denoise``: the denoising arguments of
-    fingerprint_peaks_batch."""
+    fingerprint_peaks_batch, `float32_log` among them."""
     mask, _, spec = fingerprint_peaks_batch(wav, amp_min, scale_in=scale_in, **denoise)
     # only the PEAK list is bounded by the kernel (<= 16384 peaks per clip, sorted in LDS); the hash capacity is just output memory
     dig, t1, counts = ops.dejavu_hashes(mask, cap=cap, peak_cap=min(cap, 16384) if peak_cap is None else peak_cap, fan_value=fan_value)

@@ -15,6 +15,7 @@
 //             4 frames ahead.  Latency-bound by design; parallelism comes from clips.
 #include "mfpa_common.h"
 #include "mfpa_fastlog.h"
+#include "mfpa_nplog.h"
 #include "mfpa_npsum.h"
 #include "mfpa_prepsum.h"
 
@@ -26,7 +27,10 @@ constexpr int PREP_THREADS = 512;
 constexpr int TT = 16;  // frames per transpose tile
 
 // TIn: dtype of the spectrogram (and of the log / mean arithmetic, as numpy keeps it).
-template <typename TIn>
+// NPLOG (float only): the logarithm is numpy's own float32 one (mfpa_nplog.h: the reference's np.log of the UNet output,
+// peak_extractor.py:265-276, bit for bit) instead of the float64 log rounded once to float32; the log table is then not staged.  A
+// compile-time variant: the default instantiations are the code they were without it.
+template <typename TIn, bool NPLOG = false>
 __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(const TIn* __restrict__ spec, int F, int T,
                                                                const double* __restrict__ denom, int mean_order,
                                                                int log_input, double pole,
@@ -39,9 +43,14 @@ __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(const TIn* __rest
   TIn* heap = reinterpret_cast<TIn*>(tile_out + TT * R);  // [chunks][HEAP]
   __shared__ double red[PREP_THREADS / 64];
   __shared__ double bcast[2];
-  __shared__ double logtab[128][3];                  // the log table in LDS (three dependent-address global loads per logarithm otherwise)
-  for (int i = threadIdx.x; i < 128 * 3; i += PREP_THREADS) (&logtab[0][0])[i] = (&mfpa_log_tab[0][0])[i];
-  __syncthreads();
+  static_assert(!NPLOG || sizeof(TIn) == sizeof(float), "numpy's float32 log: float32 spectrograms only");
+  // the log table in LDS (three dependent-address global loads per logarithm otherwise).  NPLOG: one unread row, kept only so that the
+  // discarded mfpa_log_t branch below still names a declared array (a static __shared__ array cannot be declared conditionally)
+  __shared__ double logtab[NPLOG ? 1 : 128][3];
+  if constexpr (!NPLOG) {
+    for (int i = threadIdx.x; i < 128 * 3; i += PREP_THREADS) (&logtab[0][0])[i] = (&mfpa_log_tab[0][0])[i];
+    __syncthreads();
+  }
 
   const int tid = threadIdx.x, b = blockIdx.x;
   const int N = F * T;
@@ -110,7 +119,8 @@ __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(const TIn* __rest
         TIn s = has_den ? (TIn)((double)v[u] / den) : v[u];
         if (do_log) {
           s = s > floor_v ? s : floor_v;
-          s = (TIn)mfpa_log_t((double)s, logtab);
+          if constexpr (NPLOG) s = mfpa_nplogf(s);
+          else s = (TIn)mfpa_log_t((double)s, logtab);
         }
         L[i] = (double)s;
       }
@@ -532,6 +542,8 @@ int mfpa_audfprint_prepare(const void* spec, int dtype, int B, int F, int T, con
   if (B == 0) return MFPA_OK;
   if (!spec || !filtered || !scratch || B < 0 || F < 2 || T < 1) return MFPA_EINVAL;
   if (dtype != MFPA_F32 && dtype != MFPA_F64) return MFPA_EINVAL;
+  const bool nplog = (log_input & MFPA_LOG_NUMPY_F32) != 0;
+  if (nplog && (dtype != MFPA_F32 || (log_input & 1) != 0)) return MFPA_EINVAL;   // a float32 log: no meaning for float64 values or caller-made logs
   if (F - 1 > 256) return MFPA_EINVAL;
   const long long N = (long long)F * T;
   if ((N + NPY_BUFSIZE - 1) / NPY_BUFSIZE > MAX_CHUNKS) return MFPA_EINVAL;
@@ -542,6 +554,9 @@ int mfpa_audfprint_prepare(const void* spec, int dtype, int B, int F, int T, con
   if (dtype == MFPA_F64)
     hipLaunchKernelGGL(prepare_kernel<double>, dim3(B), dim3(PREP_THREADS), lds, s, (const double*)spec, F, T, denom,
                        mean_order, log_input, pole, filtered, scratch);
+  else if (nplog)
+    hipLaunchKernelGGL((prepare_kernel<float, true>), dim3(B), dim3(PREP_THREADS), lds, s, (const float*)spec, F, T, denom,
+                       mean_order, log_input & 3, pole, filtered, scratch);
   else
     hipLaunchKernelGGL(prepare_kernel<float>, dim3(B), dim3(PREP_THREADS), lds, s, (const float*)spec, F, T, denom,
                        mean_order, log_input, pole, filtered, scratch);

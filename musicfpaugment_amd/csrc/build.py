@@ -26,6 +26,7 @@ COMMON = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno
 PER_FILE = {
     "audfprint.hip": ["-ffp-contract=off"],
     "dejavu.hip": ["-ffp-contract=off"],
+    "nplog.hip": ["-ffp-contract=off"],
 }
 
 

@@ -13,6 +13,7 @@
 // Compiled with -ffp-contract=off (the pre-processing feeds exact comparisons).
 #include "mfpa_common.h"
 #include "mfpa_fastlog.h"
+#include "mfpa_nplog.h"
 #include "mfpa_npsum.h"
 #include "mfpa_prepsum.h"
 
@@ -25,7 +26,9 @@ constexpr int PREP_THREADS = 1024;   // one workgroup per clip: as many waves as
 // TIn = double: the un-denoised path (psd / max, float64 throughout).  TIn = float: the UNet path (fingerprint.py:70-79) --
 // the network's float32 output is squared and every later step (max, floor max / 1e6, 10 * log, mean, subtraction) stays in
 // float32 like numpy on a float32 array; the result is widened to float64 for the peak picker (comparisons are unchanged).
-template <typename TIn>
+// NPLOG (float only): the logarithm is numpy's own float32 one (mfpa_nplog.h: np.log of the squared UNet output, fingerprint.py:78,
+// bit for bit) instead of the float64 log rounded once to float32; the log table is then not staged.  A compile-time variant.
+template <typename TIn, bool NPLOG = false>
 __global__ __launch_bounds__(PREP_THREADS) void dejavu_prepare_kernel(const TIn* __restrict__ psd, int F, int T,
                                                                       const double* __restrict__ denom, double scale,
                                                                       int mean_order, int square, double* __restrict__ arr) {
@@ -33,9 +36,14 @@ __global__ __launch_bounds__(PREP_THREADS) void dejavu_prepare_kernel(const TIn*
   TIn* heap = reinterpret_cast<TIn*>(smem);
   __shared__ double red[PREP_THREADS / 64];
   __shared__ double bcast[2];
-  __shared__ double logtab[128][3];                  // the log table in LDS (three dependent-address global loads per logarithm otherwise)
-  for (int i = threadIdx.x; i < 128 * 3; i += PREP_THREADS) (&logtab[0][0])[i] = (&mfpa_log_tab[0][0])[i];
-  __syncthreads();
+  static_assert(!NPLOG || sizeof(TIn) == sizeof(float), "numpy's float32 log: float32 input only");
+  // the log table in LDS (three dependent-address global loads per logarithm otherwise).  NPLOG: one unread row, kept only so that the
+  // discarded mfpa_log_t branch below still names a declared array (a static __shared__ array cannot be declared conditionally)
+  __shared__ double logtab[NPLOG ? 1 : 128][3];
+  if constexpr (!NPLOG) {
+    for (int i = threadIdx.x; i < 128 * 3; i += PREP_THREADS) (&logtab[0][0])[i] = (&mfpa_log_tab[0][0])[i];
+    __syncthreads();
+  }
   const int tid = threadIdx.x, b = blockIdx.x;
   const int N = F * T;
   const TIn* x = psd + (size_t)b * N;
@@ -80,7 +88,8 @@ __global__ __launch_bounds__(PREP_THREADS) void dejavu_prepare_kernel(const TIn*
       if (i0 + u * PREP_THREADS < N) {
         TIn s = value(v[u]);
         s = s > floor_v ? s : floor_v;
-        L[i0 + u * PREP_THREADS] = (double)(sc * (TIn)mfpa_log_t((double)s, logtab));   // float32: the float64 log rounded once (as audfprint.hip)
+        if constexpr (NPLOG) L[i0 + u * PREP_THREADS] = (double)(sc * mfpa_nplogf(s));   // 10 * np.log(float32 array): one float32 product
+        else L[i0 + u * PREP_THREADS] = (double)(sc * (TIn)mfpa_log_t((double)s, logtab));   // float32: the float64 log rounded once (as audfprint.hip)
       }
   }
   __syncthreads();
@@ -267,17 +276,27 @@ int mfpa_dejavu_prepare(const double* psd, int B, int F, int T, const double* de
   return MFPA_OK;
 }
 
-int mfpa_dejavu_prepare_f32(const float* x, int B, int F, int T, int square, double scale, int mean_order, double* arr,
-                            void* stream) {
+int mfpa_dejavu_prepare_f32_ex(const float* x, int B, int F, int T, int square, double scale, int mean_order, int float32_log,
+                               double* arr, void* stream) {
+  if (float32_log != MFPA_F32LOG_ROUNDED && float32_log != MFPA_F32LOG_NUMPY) return MFPA_EINVAL;
   if (B == 0) return MFPA_OK;
   if (!x || !arr || B < 0 || F < 1 || T < 1) return MFPA_EINVAL;
   const long long N = (long long)F * T;
   const long long nchunks = (N + NPY_BUFSIZE - 1) / NPY_BUFSIZE;
   if (nchunks > MAX_CHUNKS) return MFPA_EINVAL;
-  hipLaunchKernelGGL(dejavu_prepare_kernel<float>, dim3(B), dim3(PREP_THREADS), sizeof(double) * nchunks * HEAP,
-                     mfpa_stream(stream), x, F, T, (const double*)nullptr, scale, mean_order, square, arr);
+  if (float32_log == MFPA_F32LOG_NUMPY)
+    hipLaunchKernelGGL((dejavu_prepare_kernel<float, true>), dim3(B), dim3(PREP_THREADS), sizeof(double) * nchunks * HEAP,
+                       mfpa_stream(stream), x, F, T, (const double*)nullptr, scale, mean_order, square, arr);
+  else
+    hipLaunchKernelGGL(dejavu_prepare_kernel<float>, dim3(B), dim3(PREP_THREADS), sizeof(double) * nchunks * HEAP,
+                       mfpa_stream(stream), x, F, T, (const double*)nullptr, scale, mean_order, square, arr);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
+}
+
+int mfpa_dejavu_prepare_f32(const float* x, int B, int F, int T, int square, double scale, int mean_order, double* arr,
+                            void* stream) {
+  return mfpa_dejavu_prepare_f32_ex(x, B, F, T, square, scale, mean_order, MFPA_F32LOG_ROUNDED, arr, stream);
 }
 
 int mfpa_localmax2d(const double* arr, int B, int F, int T, int radius, double amp_min, uint8_t* mask,

@@ -19,6 +19,18 @@ from ._lib import F32, F64, check, lib, ptr, require_gpu, stream
 N_FFT, N_HOP, N_BINS = 512, 256, 257
 
 
+FLOAT32_LOGS = ("rounded", "numpy")
+
+
+def _float32_log_code(float32_log: str) -> int:
+    """The logarithm of the pickers' FLOAT32 (denoised) branch: "rounded" = the float64 log rounded once to float32 (the default),
+    "numpy" = numpy's own float32 log bit for bit (csrc/mfpa_nplog.h), what the reference computes at
+    afp/audfprint/peak_extractor.py:265-276 and afp/dejavu/fingerprint.py:70-79."""
+    if float32_log not in FLOAT32_LOGS:
+        raise ValueError(f"float32_log must be 'rounded' or 'numpy', got {float32_log!r}")
+    return FLOAT32_LOGS.index(float32_log)
+
+
 def _dtype_code(t: torch.Tensor) -> int:
     if t.dtype == torch.float32:
         return F32
@@ -115,6 +127,18 @@ def normalize_(data: torch.Tensor, clip_max: torch.Tensor, per_clip: bool) -> to
     return data
 
 
+def nplog_f32(x: torch.Tensor) -> torch.Tensor:
+    """Element-wise numpy float32 log (mfpa_nplog_f32): float32 tensor of any shape -> np.log(x) as numpy's SIMD kernel returns it,
+    bit for bit (csrc/mfpa_nplog.h).  For callers that post-process float32 spectrograms themselves."""
+    require_gpu(x)
+    if x.dtype != torch.float32:
+        raise TypeError("float32 expected")
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    check(lib().mfpa_nplog_f32(ptr(x), ptr(out), x.numel(), stream()), "mfpa_nplog_f32")
+    return out
+
+
 def f64_to_f32(x: torch.Tensor) -> torch.Tensor:
     require_gpu(x)
     if x.dtype != torch.float64:
@@ -152,9 +176,12 @@ def gauss_table(npoints: int, width: float, device) -> torch.Tensor:
 
 
 def audfprint_prepare(spec: torch.Tensor, denom: Optional[torch.Tensor] = None, mean_order: int = 0,
-                      log_input: bool = False, pole: float = AUDFPRINT_POLE, denom_is_clip_max: bool = False) -> torch.Tensor:
+                      log_input: bool = False, pole: float = AUDFPRINT_POLE, denom_is_clip_max: bool = False,
+                      float32_log: str = "rounded") -> torch.Tensor:
     """(B, F, T) spectrogram -> frame-major filtered log-spectrogram (B, T, F-1) float64.  `denom_is_clip_max`: denom[b] is the
-    maximum of the float64 spec[b] itself (what stft_mag returned with it), so the kernel skips its max pass."""
+    maximum of the float64 spec[b] itself (what stft_mag returned with it), so the kernel skips its max pass.  `float32_log`
+    ("rounded" | "numpy", float32 spectrograms without `log_input` only): which float32 logarithm, see _float32_log_code."""
+    nplog = 4 * _float32_log_code(float32_log)
     require_gpu(spec, "spectrogram")
     if spec.dim() != 3:
         raise ValueError("spectrogram must be (B, F, T)")
@@ -167,7 +194,7 @@ def audfprint_prepare(spec: torch.Tensor, denom: Optional[torch.Tensor] = None, 
     filtered = torch.empty((B, T, F - 1), dtype=torch.float64, device=spec.device)
     scratch = torch.empty((B, F * T), dtype=torch.float64, device=spec.device)
     check(lib().mfpa_audfprint_prepare(ptr(spec), _dtype_code(spec), B, F, T, ptr(denom), int(mean_order),
-                                       int(bool(log_input)) | (2 if (denom_is_clip_max and denom is not None and spec.dtype == torch.float64) else 0),
+                                       int(bool(log_input)) | (2 if (denom_is_clip_max and denom is not None and spec.dtype == torch.float64) else 0) | nplog,
                                        float(pole), ptr(filtered), ptr(scratch), stream()),
           "mfpa_audfprint_prepare")
     return filtered
@@ -259,17 +286,20 @@ def dejavu_pick(psd: torch.Tensor, clip_max: torch.Tensor, scale: float = 10.0, 
     return mask, npeaks
 
 
-def dejavu_prepare_f32(x: torch.Tensor, square: bool = True, scale: float = 10.0, mean_order: int = 0) -> torch.Tensor:
+def dejavu_prepare_f32(x: torch.Tensor, square: bool = True, scale: float = 10.0, mean_order: int = 0,
+                       float32_log: str = "rounded") -> torch.Tensor:
     """The denoised branch of Dejavu's pre-processing (fingerprint.py:70-79): float32 (B, F, T) network output -> x**2 ->
-    10*log(max(., max/1e6)) - mean in float32, widened to float64 for the picker."""
+    10*log(max(., max/1e6)) - mean in float32, widened to float64 for the picker.  `float32_log` ("rounded" | "numpy"): which
+    float32 logarithm, see _float32_log_code."""
+    log_mode = _float32_log_code(float32_log)
     require_gpu(x, "x")
     if x.dim() != 3 or x.dtype != torch.float32:
         raise ValueError("x must be (B, F, T) float32")
     x = x.contiguous()
     B, F, T = x.shape
     arr = torch.empty((B, F, T), dtype=torch.float64, device=x.device)
-    check(lib().mfpa_dejavu_prepare_f32(ptr(x), B, F, T, int(bool(square)), float(scale), int(mean_order), ptr(arr),
-                                        stream()), "mfpa_dejavu_prepare_f32")
+    check(lib().mfpa_dejavu_prepare_f32_ex(ptr(x), B, F, T, int(bool(square)), float(scale), int(mean_order), log_mode, ptr(arr),
+                                           stream()), "mfpa_dejavu_prepare_f32_ex")
     return arr
 
 

@@ -62,18 +62,21 @@ class HotPath:
     """picker "audfprint": STFT -> /max -> [UNet] -> log / mean / high-pass -> decaying-threshold prune (peak_extractor.py:236-311);
     picker "dejavu": specgram PSD -> /max -> [UNet, squared] -> 10 ln / mean -> 21 x 21 local maxima (fingerprint.py:56-171)."""
 
-    def __init__(self, unet, device="cuda", picker: str = "audfprint", streams: int = 1):
+    def __init__(self, unet, device="cuda", picker: str = "audfprint", streams: int = 1, float32_log: str = "rounded"):
         """`streams` > 1: consecutive calls run on `streams` HIP streams in turn, so that batch k + 1's STFT overlaps batch k's pruner
         (one wavefront per clip: at 256 clips it leaves the card almost empty for 263 us of a 449 us batch).  Every call still waits
         for the work the caller has queued on the current stream (its input); the RESULTS of such calls are ordered behind the current
-        stream only by `join()` -- call it before reading them.  The kernels and their results are the serial path's (per-call buffers)."""
+        stream only by `join()` -- call it before reading them.  The kernels and their results are the serial path's (per-call buffers).
+        `float32_log` ("rounded" | "numpy"): the logarithm taken of the UNet's float32 output by either picker -- "numpy" is numpy's own
+        float32 log bit for bit (the reference's arithmetic), "rounded" (the default) the float64 log rounded once to float32."""
+        ops._float32_log_code(float32_log)
         if picker not in ("audfprint", "dejavu"):
             raise ValueError("picker must be 'audfprint' or 'dejavu'")
         if streams < 1:
             raise ValueError("streams must be >= 1")
-        self.picker, self.unet = picker, unet
+        self.picker, self.unet, self.float32_log = picker, unet, float32_log
         self.extractor = Audfprint_peaks(None, denoising=unet is not None, denoising_model="unet" if unet else None,
-                                         unet=unet, device=device)
+                                         unet=unet, device=device, float32_log=float32_log)
         self._side = [torch.cuda.Stream(device=device) for _ in range(streams)] if streams > 1 else []
         self._turn = 0
 
@@ -82,7 +85,7 @@ class HotPath:
         if self.picker == "dejavu":
             from .afp.dejavu.fingerprint import fingerprint_peaks_batch
             mask, npeaks, _ = fingerprint_peaks_batch(wav, denoising=self.unet is not None, denoising_model="unet", unet=self.unet,
-                                                      want_spec=False)
+                                                      want_spec=False, float32_log=self.float32_log)
             return mask, npeaks
         mask, npeaks, _ = self.extractor.find_peaks_batch(wav, want_spec=False)
         return mask, npeaks

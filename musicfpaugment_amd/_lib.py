@@ -268,7 +268,7 @@ def lib() -> ctypes.CDLL:
 
 
 def set_library_path(path: str) -> None:
-    """tools/ and tests only: bind another build of the library (e.g. libmfpa_exp.so, the -DMFPA_EXPERIMENTS build) before the
+    """tools/ and tests only: bind another build of the library (e.g. an earlier commit's, for a same-call comparison) before the
     first call.  The product path never calls this, and no environment variable redirects the library."""
     global LIB_PATH, _lib
     if _lib is not None:

@@ -50,17 +50,13 @@ def _stamp(src: str, flags) -> str:
     return h.hexdigest()
 
 
-def build(force: bool = False, verbose: bool = True, experiments: bool = False, extra_flags=(), out: str = None) -> str:
-    """experiments=True: the A/B build of tools/ (-DMFPA_EXPERIMENTS: the environment switches of mfpa_common.h are live) ->
-    libmfpa_exp.so, which the package never loads on its own.  `extra_flags` / `out`: further tools-only variants."""
-    OUT = out or (os.path.join(PKG, "libmfpa_exp.so") if experiments else globals()["OUT"])
-    OBJ = os.path.join(HERE, "build" + ("_exp" if experiments else "") + ("_" + hashlib.sha1(" ".join(extra_flags).encode()).hexdigest()[:8] if extra_flags else ""))
+def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
     jobs = []
     objs = []
     for src in _sources():
-        flags = COMMON + PER_FILE.get(src, []) + (["-DMFPA_EXPERIMENTS"] if experiments else []) + list(extra_flags)
+        flags = COMMON + PER_FILE.get(src, [])
         obj = os.path.join(OBJ, src.replace(".hip", ".o"))
         stamp_file = obj + ".stamp"
         stamp = _stamp(src, flags)
@@ -90,8 +86,7 @@ def build(force: bool = False, verbose: bool = True, experiments: bool = False, 
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
-    if OUT == globals()["OUT"]:
-        write_record(record(OUT))
+    write_record(record(OUT))
     return OUT
 
 
@@ -119,4 +114,4 @@ def record(path: str = None) -> dict:
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, experiments="--experiments" in sys.argv))
+    print(build(force="--force" in sys.argv))

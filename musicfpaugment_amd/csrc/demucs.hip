@@ -15,6 +15,7 @@
 // The 1-channel ends (first Conv1d, last ConvTranspose1d), the sinc x2 resamplers and the std normalisation are
 // small VALU kernels.
 #include "mfpa_common.h"
+#include "mfpa_conv_tile.h"
 #include <type_traits>
 
 namespace {
@@ -526,15 +527,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_wide_kernel(GemmArgs a) {
 // code per chunk parity, so hipcc's vmcnt bookkeeping is exact: no s_waitcnt vmcnt(0) in the steady state).  Rows past M are
 // clamped to row M - 1 when loaded (never stored), so every load is unconditional.  K must be a multiple of 64, at least 128.
 constexpr int PBM = 256;
-template <int SLOTS, int LEFT, int I = 0>
-__device__ __forceinline__ void g_pin_reads() {          // "one MFMA, then k LDS reads", LEFT reads spread over SLOTS MFMAs
-  if constexpr (I < SLOTS && LEFT > 0) {
-    constexpr int k = (LEFT + (SLOTS - I) - 1) / (SLOTS - I);
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, k, 0);
-    g_pin_reads<SLOTS, LEFT - k, I + 1>();
-  }
-}
+using mfpa_tile::pin_reads;       // "one MFMA, then k LDS reads", LEFT reads spread over SLOTS MFMAs
 
 template <bool WSPLIT>
 __global__ __launch_bounds__(512, 1) void gemm_bf16x3_pipe_kernel(GemmArgs a) {
@@ -631,7 +624,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16x3_pipe_kernel(GemmArgs a) {
     mfma12(fr0);
     if constexpr (STORE) store(SET ^ 1, other);
     if constexpr (LOAD) load(cur, kc + 3, other);
-    g_pin_reads<8, 8>();
+    pin_reads<8, 8>();
     if constexpr (STORE) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x200, N_DSW / 2, 0);
@@ -652,7 +645,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16x3_pipe_kernel(GemmArgs a) {
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (STORE) read_frags(fr0, SET ^ 1, 0);
     mfma12(fr1);
-    if constexpr (STORE) g_pin_reads<12, 8>();
+    if constexpr (STORE) pin_reads<12, 8>();
     __builtin_amdgcn_sched_barrier(0);
   };
   using T = std::true_type;

@@ -7,24 +7,6 @@
 
 #define MFPA_WAVE 64
 
-// Experiment switches (A/B timing runs of tools/, some of which skip work and give WRONG results) exist only in a library
-// built with -DMFPA_EXPERIMENTS (`python -m musicfpaugment_amd.csrc.build --experiments` -> libmfpa_exp.so, never loaded by the
-// package on its own).  The product library does not read the environment: every switch is its compile-time default.
-#ifdef MFPA_EXPERIMENTS
-#include <cstdlib>
-#define MFPA_EXP_ENV(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-#define MFPA_EXP_FLAG(word, bit) (((word) & (bit)) != 0)
-#elif defined(MFPA_SKIP_BITS)
-// timing-only variants of the PRODUCT code (tools/: `build(extra_flags=["-DMFPA_SKIP_BITS=<bits>"], out=...)`): the skip switches of the
-// experiments build as compile-time constants, so that the variant differs from the shipped kernel by the skipped work only (the
-// run-time switches cost conv_wd16_kernel's 64-channel form 12 % by themselves).  Wrong results by design; never loaded by the package.
-#define MFPA_EXP_ENV(name, dflt) (dflt)
-#define MFPA_EXP_FLAG(word, bit) (((MFPA_SKIP_BITS) & (bit)) != 0)
-#else
-#define MFPA_EXP_ENV(name, dflt) (dflt)
-#define MFPA_EXP_FLAG(word, bit) false
-#endif
-
 #define MFPA_CHECK_LAUNCH()                                   \
   do {                                                        \
     hipError_t e__ = hipGetLastError();                       \

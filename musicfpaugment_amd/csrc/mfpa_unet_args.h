@@ -39,9 +39,6 @@ struct ConvArgs {
   const float* bz_invstd;
   float* stats_part;                 // conv_wd16_kernel: optional per-wave partial (sum, sum of squares) of the stored output per channel:
                                      //   [tile * WMW + wm][2][Cout] (mfpa_conv_desc.stats_part; rows = mfpa_conv_stats_rows())
-  int dbg_stagger;                   // -DMFPA_EXPERIMENTS builds only: start delay of persistent workgroup k = (k & 7) x this x 4096 cycles
-  int dbg_lds_stamps;                // -DMFPA_EXPERIMENTS builds only: LDS byte offset of the tap-timeline stamps (0 = none)
-  int dbg;                           // -DMFPA_EXPERIMENTS builds only (MFPA_CONV_DBG): 1 skip B staging, 2 skip barriers, 4 skip stores, 8 skip MFMA, 16 skip halo staging
   // C1SRC: source 0 is not read but COMPUTED while it is staged -- the UNet's first layer (1 -> 64 channels, folded BN,
   // ReLU) applied to the normalised spectrogram, so its 64-channel output never exists in HBM
   const float* c1_x32;               // (B,H,W) float32, or

@@ -17,32 +17,12 @@
 // Global loads of the next tap's weights (and next chunk's halo) are issued before the MFMA
 // block of the current tap and written to LDS after it, so they overlap the matrix work.
 #include "mfpa_common.h"
+#include "mfpa_conv_tile.h"
 #include "mfpa_unet_args.h"
-
-#include <cstdlib>
-#include <type_traits>
 
 namespace {
 
-#ifdef MFPA_EXPERIMENTS
-// In-kernel timeline (experiments build only; tools/exp_conv_timeline.py): every workgroup's wave 0 stamps s_memrealtime (100 MHz) at five points
-// into a buffer whose address the tool stores in this device symbol.  No output value depends on a stamp.
-__device__ unsigned long long* mfpa_conv_stamps = nullptr;
-#define MFPA_STAMP(slot)                                                                                                   \
-  do {                                                                                                                     \
-    if (mfpa_conv_stamps && threadIdx.x == 0)                                                                              \
-      mfpa_conv_stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime();   \
-  } while (0)
-#else
-#define MFPA_STAMP(slot) do { } while (0)
-#endif
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace mfpa_tile;     // vector types, pin_reads / pin_read_slots
 
 // PREC 1 weight image ("w3", built by ops_unet.split_bf16x3 / mfpa_pack_conv_weights): [tap][chunk][row][128 B], one row =
 // the 32 channels of a chunk as 8 slots of 16 B, logical slots 0-3 = 32 bf16 hi, 4-7 = 32 bf16 lo, stored at PHYSICAL slot
@@ -53,27 +33,6 @@ __device__ __forceinline__ int w3_swz(int row) { return (row >> 1) & 7; }
 
 constexpr int KC = 32;        // channels per K chunk
 constexpr int LDK = KC + 4;   // padded LDS row (floats): 144 B -> conflict-free b128 fragment reads
-
-__device__ __forceinline__ bool v_never(float v) { return v != 12345.678f; }  // keeps the accumulators live in the 'skip stores' experiment
-
-// sched_group_barrier pattern "one MFMA, then k LDS reads" with LEFT reads spread evenly over SLOTS MFMAs
-template <int SLOTS, int LEFT, int I = 0>
-__device__ __forceinline__ void pin_reads() {
-  if constexpr (I < SLOTS && LEFT > 0) {
-    constexpr int k = (LEFT + (SLOTS - I) - 1) / (SLOTS - I);
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, k, 0);
-    pin_reads<SLOTS, LEFT - k, I + 1>();
-  }
-}
-constexpr int pin_read_slots(int slots, int left) {      // how many MFMAs pin_reads placed
-  int used = 0;
-  for (int i = 0; i < slots && left > 0; ++i) {
-    left -= (left + (slots - i) - 1) / (slots - i);
-    ++used;
-  }
-  return used;
-}
 
 // does this instantiation run the software-pipelined main loop (the bf16x3 3x3 convolution on 8 waves: one workgroup per CU, two
 // halo stages)?
@@ -132,7 +91,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_
   float* Sp = Bs0 + 2 * B_STAGE;                      // [SH][SW]
   float* W1s = Sp + SH * SW;                          // [9][64]
 
-  MFPA_STAMP(0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave % WM, wn = wave / WM;
   const int li = lane & 31, lh = lane >> 5;
@@ -414,17 +372,15 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_
   // one pipeline iteration of MODE 2, whose A tile changes with the tap; register set CUR holds B(it+1), the other set receives B(it+2)
   auto step = [&](int it, auto CUR) __attribute__((always_inline)) {
     constexpr int cur = decltype(CUR)::value;
-    if (!MFPA_EXP_FLAG(a.dbg, 1)) {
-      if (it + 1 < nit) store_b(CUR, Bs0 + ((it + 1) & 1) * (BN * LDK));
-      if (it + 2 < nit) load_b(it + 2, std::integral_constant<int, 1 - cur>{});
-    }
+    if (it + 1 < nit) store_b(CUR, Bs0 + ((it + 1) & 1) * (BN * LDK));
+    if (it + 2 < nit) load_b(it + 2, std::integral_constant<int, 1 - cur>{});
     if (it + 1 < nit) load_a((it + 1) / TAPS, (it + 1) % TAPS);
-    if (!MFPA_EXP_FLAG(a.dbg, 8)) compute(0, Bs0 + (it & 1) * (BN * LDK));
+    compute(0, Bs0 + (it & 1) * (BN * LDK));
     if (it + 1 < nit) {
-      if (!MFPA_EXP_FLAG(a.dbg, 2)) __syncthreads();            // every wave is done reading As
+      __syncthreads();            // every wave is done reading As
       store_a((it + 1) / TAPS, As);
     }
-    if (!MFPA_EXP_FLAG(a.dbg, 2)) __syncthreads();
+    __syncthreads();
   };
 
   // The same iteration with the tap (and the parity of `it`, i.e. the weight register set and LDS stage) as compile-time constants:
@@ -435,18 +391,16 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_
     constexpr int tap = decltype(TAP_)::value, par = decltype(PAR_)::value;
     constexpr int tap_off = ((tap / 3) * HPW + (tap % 3)) * LDK;
     const bool more = chunk + 1 < nchunks;                               // a chunk follows this one
-    if (!MFPA_EXP_FLAG(a.dbg, 1)) {
-      if (tap + 1 < TAPS || more) store_b(std::integral_constant<int, par>{}, Bs0 + (par ^ 1) * (BN * LDK));
-      if (tap + 2 < TAPS) load_b_at(chunk, tap + 2, std::integral_constant<int, 1 - par>{});
-      else if (more) load_b_at(chunk + 1, tap + 2 - TAPS, std::integral_constant<int, 1 - par>{});
-    }
+    if (tap + 1 < TAPS || more) store_b(std::integral_constant<int, par>{}, Bs0 + (par ^ 1) * (BN * LDK));
+    if (tap + 2 < TAPS) load_b_at(chunk, tap + 2, std::integral_constant<int, 1 - par>{});
+    else if (more) load_b_at(chunk + 1, tap + 2 - TAPS, std::integral_constant<int, 1 - par>{});
     if (tap == 0 && more) load_a(chunk + 1, 0);
-    if (!MFPA_EXP_FLAG(a.dbg, 8)) compute(tap_off, Bs0 + par * (BN * LDK));
+    compute(tap_off, Bs0 + par * (BN * LDK));
     if (tap == TAPS - 1 && more) {
-      if (!MFPA_EXP_FLAG(a.dbg, 2)) __syncthreads();
+      __syncthreads();
       store_a(chunk + 1, As);
     }
-    if (!MFPA_EXP_FLAG(a.dbg, 2)) __syncthreads();
+    __syncthreads();
   };
   auto chunk_s = [&](auto PAR0_, int chunk) __attribute__((always_inline)) {      // nine taps; PAR0 = parity of the chunk's first iteration
     constexpr int p0 = decltype(PAR0_)::value;
@@ -543,25 +497,23 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_
     read_frags(fr1, Asb, Bsb, tap_off, 1);
     mfma_lo(fr0);
     mfma_hi(fr0);
-    if (!MFPA_EXP_FLAG(a.dbg, 1)) {
-      store_b(std::integral_constant<int, (tap + 1) % 3>{}, Bsn);
-      constexpr int t3 = (tap + 3) % TAPS;
-      const int c3 = (tap + 3 >= TAPS) ? chunk_n : chunk;
-      load_b_ct(c3, t3, std::integral_constant<int, tap % 3>{});
-    }
+    store_b(std::integral_constant<int, (tap + 1) % 3>{}, Bsn);
+    constexpr int t3 = (tap + 3) % TAPS;
+    const int c3 = (tap + 3 >= TAPS) ? chunk_n : chunk;
+    load_b_ct(c3, t3, std::integral_constant<int, tap % 3>{});
     pin_phase(std::true_type{});
     __builtin_amdgcn_sched_barrier(0);
-    if (!MFPA_EXP_FLAG(a.dbg, 2)) __syncthreads();
+    __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
     // ---- phase B: (tap 0: issue the loads of the next chunk's halo)  read frags(it+1, s=0) -> F0 || MFMA(F1)
     //      (tap 2: split that halo into the OTHER halo stage)
-    if (tap == 0 && !MFPA_EXP_FLAG(a.dbg, 16)) load_a(chunk_n, 0);
+    if (tap == 0) load_a(chunk_n, 0);
     read_frags(fr0, Asn, Bsn, ntap_off, 0);          // past the end: a harmless read of valid LDS
     mfma_lo(fr1);
     mfma_hi(fr1);
     pin_phase(std::false_type{});
     __builtin_amdgcn_sched_barrier(0);
-    if (tap == 2 && !MFPA_EXP_FLAG(a.dbg, 16)) store_a(chunk_n, As + ((chunk + 1) & 1) * (HPS * LDK));
+    if (tap == 2) store_a(chunk_n, As + ((chunk + 1) & 1) * (HPS * LDK));
   };
 
   if (C1SRC) {
@@ -578,7 +530,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_
     for (int i = tid; i < 9 * 64; i += THREADS) W1s[i] = a.c1_w[i];
     __syncthreads();
   }
-  MFPA_STAMP(1);                                       // C1SRC: the spectrogram patch and the first layer's weights are staged
   load_a(0, 0);
   if constexpr (PIPE) {
     using Set2 = std::integral_constant<int, 2>;
@@ -606,7 +557,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_
     store_b(Set0{}, Bs0);
     if (nit > 1) load_b(1, Set0{});
     __syncthreads();
-    MFPA_STAMP(2);                                     // first halo tile (C1SRC: the first layer on it) and weight tile in LDS
     if constexpr (MODE == 0) {
       // nine is odd: the parity of a chunk's first iteration alternates from chunk to chunk
       int chunk = 0;
@@ -623,7 +573,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_
     }
   }
 
-  MFPA_STAMP(3);                                       // main loop done
   // epilogue: out = relu(acc * scale[n] + shift[n]); D[row = pixel][col = channel]
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
@@ -659,7 +608,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_
           char* yp = yb + (pix * cout * 4u + nb);
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt)
-            if (!(MFPA_EXP_FLAG(a.dbg, 4) && v_never(acc[mt][nt][r]))) *reinterpret_cast<float*>(yp + nt * 128) = acc[mt][nt][r];
+            *reinterpret_cast<float*>(yp + nt * 128) = acc[mt][nt][r];
         }
       }
     }
@@ -732,7 +681,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_
       if (gy < a.H && gx < a.W) a.y1x1[((size_t)b * a.H + gy) * a.W + gx] = p + a.b1x1;
     }
   }
-  MFPA_STAMP(4);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -752,7 +700,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_mfma_
 //   image: [tap][chunk = Cin / 32][Cout / 16][hi | lo][lane 64][16 B], lane (g = l >> 4, c = l & 15) = channel 16 t + c, k 32 chunk + 8 g .. + 7
 //          (ops_unet.split_bf16x3_frag(w, 2), mfpa_pack_conv_weights(precision 3)).
 // Not bit-identical to the 32 x 32 x 16 kernels (a k-step sums 32 products inside the instruction); same products, fp32 accumulate.
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_row_add(float v) {               // v + (v of the lane CTRL names; 0 where there is none)
@@ -852,24 +799,6 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pb), 0, base != nullptr ? (int)clip_bytes : 0, 0x00020000);
   };
   int tile = blockIdx.x;
-#ifdef MFPA_EXPERIMENTS
-  // tap-level timeline (tools/exp_c64_timeline.py): wave 0 of workgroup (17, 0) stamps s_memtime at every tap start / epilogue start / end of
-  // its first tiles into LDS (tag in the low 8 bits), dumped to the stamp buffer when the kernel ends
-  unsigned long long* const tsbuf = reinterpret_cast<unsigned long long*>(smem + a.dbg_lds_stamps);
-  int stamp_n = 0;
-  const bool stamping = PERSIST && mfpa_conv_stamps != nullptr && a.dbg_lds_stamps != 0 && blockIdx.x == 17 && blockIdx.y == 0 && tid == 0;
-  auto stamp = [&](int tag) __attribute__((always_inline)) {
-    if (stamping && stamp_n < 500) tsbuf[stamp_n++] = (__builtin_amdgcn_s_memtime() & ~0xffull) | (unsigned)tag;
-  };
-#else
-  auto stamp = [](int) {};
-#endif
-#ifdef MFPA_EXPERIMENTS
-  if (PERSIST && a.dbg_stagger > 0) {                                  // experiment: de-synchronise the CUs' tile periods
-    const int units = (int)(blockIdx.x & 7u) * a.dbg_stagger;
-    for (int i = 0; i < units; ++i) __builtin_amdgcn_s_sleep(64);      // 64 x 64 cycles per unit
-  }
-#endif
   Tile S = make_tile(tile);                                            // the tile whose halo is being requested / split
   int eb = S.b, ey0 = S.y0, ex0p = S.x0p;                              // the tile being computed (epilogue coordinates)
   // training forward: the producer's per-channel (scale, shift) of source 0, copied to LDS once ([scale C0 | shift C0])
@@ -906,7 +835,6 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
       areg[it % AREGS] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(ao[it * THREADS] + toff), 0, 0));
   };
   auto load_a = [&](int chunk) __attribute__((always_inline)) {
-    if (MFPA_EXP_FLAG(a.dbg, 64)) return;
     load_a_range(chunk, std::integral_constant<int, 0>{}, std::integral_constant<int, AREGS>{});
   };
   // tap-by-tap forms: the slot offsets of the chunk requested at the next tap 0 are read from the LDS table one tap EARLIER (tap 8, when
@@ -918,7 +846,6 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
     for (int it = 0; it < A_F4; ++it) areg[it % AREGS][0] = __uint_as_float(ao[it * THREADS]);
   };
   auto load_a_pre = [&](int chunk) __attribute__((always_inline)) {
-    if (MFPA_EXP_FLAG(a.dbg, 64)) return;
     const int c0 = chunk * KC;
     const bool from0 = c0 < a.C0;
     const auto rs = clip_rsrc(from0 ? a.x0 : a.x1, S.b, from0 ? clip0 : clip1);
@@ -1135,20 +1062,18 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
     const int chunk_n = chunk + 1 < nchunks ? chunk + 1 : 0;          // past the tile's last chunk: chunk 0 of the next tile (S is that tile by then)
     const char* cur = smem + (chunk & 1) * STAGE;
     const char* nxt = (tap == TAPS - 1) ? smem + ((chunk + 1) & 1) * STAGE : cur;
-    stamp(tap);
     if (tap == TAPS - 1) {
       __syncthreads();                                                 // the next stage is complete, this one is read out
       __builtin_amdgcn_sched_barrier(0);
-      stamp(9);
     }
     if (tap == 0) load_a_pre(chunk_n);
     // what the next tap 0 requests: chunk + 2; from the tile's last-but-one chunk on, the next tile's chunk 0, then its chunk 1
     if (tap == TAPS - 1) preload_offsets(chunk + 2 < nchunks ? chunk + 2 : chunk + 1 < nchunks ? 0 : 1 < nchunks ? 1 : 0);
     read_x(par ? fx0 : fx1, nxt, ntap_off, 0);
-    if (!MFPA_EXP_FLAG(a.dbg, 8)) mfma_half(par ? fx1 : fx0, wq[tap % 3], 0);
-    if (!MFPA_EXP_FLAG(a.dbg, 128)) load_w((tap + 2 >= TAPS) ? chunk_n : chunk, (tap + 2) % TAPS, std::integral_constant<int, (tap + 2) % 3>{});
+    mfma_half(par ? fx1 : fx0, wq[tap % 3], 0);
+    load_w((tap + 2 >= TAPS) ? chunk_n : chunk, (tap + 2) % TAPS, std::integral_constant<int, (tap + 2) % 3>{});
     if constexpr (tap >= 2 && tap - 2 < A_F4) {
-      if (!MFPA_EXP_FLAG(a.dbg, 256)) split_slot(std::integral_constant<int, tap - 2>{}, chunk_n, smem + ((chunk + 1) & 1) * STAGE);
+      split_slot(std::integral_constant<int, tap - 2>{}, chunk_n, smem + ((chunk + 1) & 1) * STAGE);
 #pragma unroll
       for (int i = 0; i < N_R; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -1452,8 +1377,7 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
             f32x4 o;
   #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = acc[ct][pt][j];
-            if (MFPA_EXP_FLAG(a.dbg, 512)) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(yp + ct * 64));
-            else if (!(MFPA_EXP_FLAG(a.dbg, 4) && v_never(o[0] + o[3]))) *reinterpret_cast<f32x4*>(yp + ct * 64) = o;
+            *reinterpret_cast<f32x4*>(yp + ct * 64) = o;
           }
           }
           if (SIDE && a.y_bf16 != nullptr) {
@@ -1588,9 +1512,7 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
         tap_body4(std::integral_constant<int, 7>{}, S1{}, chunk + 1);
         tap_body4(std::integral_constant<int, 8>{}, S1{}, chunk + 1);
       }
-      stamp(10);
-      if (!(MFPA_EXP_FLAG(a.dbg, 32) && v_never(acc[0][0][0] + acc[1][PT - 1][3]))) epilogue();
-      stamp(11);
+      epilogue();
       if (!has_next) break;
       tile = tile_n; eb = S.b; ey0 = S.y0; ex0p = S.x0p;
 #pragma unroll
@@ -1598,12 +1520,6 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
 #pragma unroll
         for (int pt = 0; pt < PT; ++pt) acc[ct][pt] = floatx4{0.f, 0.f, 0.f, 0.f};
     }
-#ifdef MFPA_EXPERIMENTS
-    if (stamping) {
-      for (int i = 0; i < stamp_n; ++i) mfpa_conv_stamps[1 + i] = tsbuf[i];
-      mfpa_conv_stamps[0] = stamp_n;
-    }
-#endif
   } else if constexpr (PERSIST) {                                    // WMW = 2, tap-by-tap, persistent
     read_x(fx0, smem, 0, 0);
     for (;;) {
@@ -1656,10 +1572,6 @@ template <int PH, int PW, int WMW = 2>
 int launch_wd16(ConvArgs& a, hipStream_t s) {
   a.tiles_x = (a.W + PW - 1) / PW;
   a.tiles_y = (a.H + PH - 1) / PH;
-  static const int dbg_env = MFPA_EXP_ENV("MFPA_CONV_DBG", 0);         // experiments builds: 8 skip MFMAs, 32 skip the epilogue, 64 skip halo loads,
-  a.dbg = dbg_env;                                                     //   128 weight loads in the prologue only, 256 skip the halo split
-  static const int stagger_env = MFPA_EXP_ENV("MFPA_CONV_STAGGER", 0);
-  a.dbg_stagger = stagger_env;
   if ((long long)a.tiles_x * a.tiles_y * a.B > 0x7fffffffLL) return MFPA_EINVAL;
   constexpr int HP = (PW + 2) * (PH + 2);
   constexpr int A_F4 = (HP * (KC / 4) + 511) / 512;
@@ -1670,10 +1582,6 @@ int launch_wd16(ConvArgs& a, hipStream_t s) {
                      (a.w1x1 ? (size_t)2 * 256 * sizeof(float) : 0) +                                                             // + the fused OutConv's partial sums
                      (size_t)(2 * 32 * (8 / WMW) + 64) * sizeof(float);                                                           // + the epilogue's constants
   dim3 grid((unsigned)((long long)a.tiles_x * a.tiles_y * a.B), (unsigned)(a.Cout / (32 * (8 / WMW))));
-#ifdef MFPA_EXPERIMENTS
-  a.dbg_lds_stamps = (int)lds;
-  const_cast<size_t&>(lds) += 4096;
-#endif
   const int cin = a.C0 + a.C1;
   const bool side = a.x0_bf16 || a.x1_bf16 || a.y_bf16 || a.stats_part;
   const bool rows = WMW == 2 && cin % 64 == 0 && cin >= CONV_WD16_ROWS;
@@ -1705,8 +1613,7 @@ int launch_wd16(ConvArgs& a, hipStream_t s) {
     } else if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 4, true>), grid, dim3(512), lds, s, a);
     else hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 4, false>), grid, dim3(512), lds, s, a);
   } else if (a.plain) {
-    static const int plain_rows = MFPA_EXP_ENV("MFPA_CONV_PLAIN_ROWS", 1);      // experiments: 0 = the tap-by-tap loop
-    if (plain_rows && cin % 64 == 0) {
+    if (cin % 64 == 0) {
       if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, true, 2, true, true>), grid, dim3(512), lds, s, a);
       else hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, true, 2, false, true>), grid, dim3(512), lds, s, a);
     } else if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 2, true, true>), grid, dim3(512), lds, s, a);
@@ -2133,8 +2040,6 @@ int launch_conv(ConvArgs& a, hipStream_t s) {
   constexpr int HP = (PW + 2 * HALO) * (PH + 2 * HALO);
   a.tiles_x = (a.W + PW - 1) / PW;
   a.tiles_y = (a.H + PH - 1) / PH;
-  static const int dbg_env = MFPA_EXP_ENV("MFPA_CONV_DBG", 0);
-  a.dbg = dbg_env;
   if ((long long)a.tiles_x * a.tiles_y * a.B > 0x7fffffffLL) return MFPA_EINVAL;
   constexpr bool PIPE = conv_is_pipe(WM, WN, MODE, PREC);           // the kernel's PIPE: two padded halo stages
   constexpr int THREADS = 64 * WM * WN;
@@ -2323,12 +2228,6 @@ int mfpa_conv_mfma(const mfpa_conv_desc* d, void* stream) {
   if (d->mode == 1) return dispatch_conv<1>(a, s, prec);
   return dispatch_conv<2>(a, s, prec);
 }
-
-#ifdef MFPA_EXPERIMENTS
-int mfpa_exp_conv_stamps(unsigned long long* buf) {       // experiments build only (not in include/mfpa.h): timeline buffer, 8 slots per workgroup
-  return hipMemcpyToSymbol(HIP_SYMBOL(mfpa_conv_stamps), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 int mfpa_conv_c1_layout(int H, int W) {
   if (H < 1 || W < 1) return MFPA_EINVAL;

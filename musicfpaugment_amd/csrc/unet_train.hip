@@ -548,7 +548,8 @@ struct WgradArgs {
   int tiles_x, tiles_y;
   unsigned drop_seed, drop_thresh;
   float drop_scale;
-  int xcd;                  // bf16 kernels: XCD-aware (patch group, tile) order
+  int xcd;                  // bf16 kernels: XCD-aware (patch group, tile) order.  Always 1 (the plain order was an experiment, retired); the field and its
+                            // test stay because without them hipcc allocates the wgrad kernels' registers differently
 };
 
 constexpr int WG_PH = 2, WG_PW = 32, WG_PIX = 64, WG_T = 64;
@@ -697,8 +698,7 @@ __device__ __forceinline__ void wg_store_split(char* row, int c4, f32x4 v) {
 // 8 waves: (co half) x (ci half) x (pixel half of a 128-pixel patch, 4x32 or 8x16 for narrow images); one workgroup
 // per CU, two waves per SIMD.
 
-// NW = 8: one workgroup per CU on 128-pixel patches; NW = 4: 64-pixel patches, two workgroups per CU whose staging and
-// MFMA phases overlap each other.
+// NW = 8 (the only form launched): one workgroup per CU on 128-pixel patches.
 // PLAIN: one bf16 MFMA per product (precision 2) -- only the hi halves are staged (192-byte pixel rows: 128 B + 64 B pad keep
 // the four rows of a transposing block on bank offsets 0 / 192 / 128 / 64).  A weight gradient sums over every pixel of the
 // batch, so the 2^-9 rounding of the products averages out (relative L1 2e-3 vs fp32 on one layer, the level of fp32
@@ -1947,30 +1947,28 @@ int mfpa_wgrad_mfma(const mfpa_wgrad_desc* d, void* stream) {
   if (d->precision == 3 && (d->in_scale0 || d->drop_thresh)) return MFPA_EINVAL;      // bf16 operands are already activated
   if (d->precision >= 1) {
     // transposing LDS reads need every lane live (512-thread workgroups, no early exits) -- guaranteed by the kernel shape
-    static const int nw_env = MFPA_EXP_ENV("MFPA_WGRAD_NW", 0);   // experiments: 4 or 8 waves
-    const int nw = (d->precision != 3 && (nw_env == 4 || nw_env == 8)) ? nw_env : 8;
+    constexpr int nw = 8;
     const int pix = 16 * nw;
     const int pw = d->W <= 16 ? 16 : 32, phh = pix / pw;
     a.tiles_x = (d->W + pw - 1) / pw;
     a.tiles_y = (d->H + phh - 1) / phh;
     const long long npatch_b = (long long)a.B * a.tiles_x * a.tiles_y;
-    long long split_b = ((nw == 8 ? 1024 : 2048) + tiles - 1) / tiles;   // ~4 workgroup rounds over the launch
+    long long split_b = (1024 + tiles - 1) / tiles;   // ~4 workgroup rounds over the launch
     if (split_b > npatch_b) split_b = npatch_b;
     if (split_b < 1) split_b = 1;
     if (split_b > 65535) split_b = 65535;
     grid.z = (unsigned)split_b;
-    static const int xcd_env = MFPA_EXP_ENV("MFPA_GEMM_XCD", 1);   // 0: plain order (experiments)
-    a.xcd = xcd_env;
+    a.xcd = 1;
     const bool plain = d->precision >= 2;
     const size_t lds = (size_t)(plain ? 192 : WGB_ROW) * ((d->mode == 1 && d->precision == 3 ? 4 : 1) * pix + (d->mode == 0 ? (phh + 2) * (pw + 2) : pix));
     const dim3 blk(64 * nw);
-#define MFPA_WG_LAUNCH(M, P, N, Q) hipLaunchKernelGGL((wgrad_bf16x3_kernel<M, P, N, Q>), grid, blk, lds, s, a)
-#define MFPA_WG_PICK(N, Q)                                  \
+#define MFPA_WG_LAUNCH(M, P, Q) hipLaunchKernelGGL((wgrad_bf16x3_kernel<M, P, nw, Q>), grid, blk, lds, s, a)
+#define MFPA_WG_PICK(Q)                                     \
     do {                                                    \
-      if (d->mode == 0 && pw == 32) MFPA_WG_LAUNCH(0, 32, N, Q); \
-      else if (d->mode == 0) MFPA_WG_LAUNCH(0, 16, N, Q);   \
-      else if (pw == 32) MFPA_WG_LAUNCH(1, 32, N, Q);       \
-      else MFPA_WG_LAUNCH(1, 16, N, Q);                     \
+      if (d->mode == 0 && pw == 32) MFPA_WG_LAUNCH(0, 32, Q); \
+      else if (d->mode == 0) MFPA_WG_LAUNCH(0, 16, Q);      \
+      else if (pw == 32) MFPA_WG_LAUNCH(1, 32, Q);          \
+      else MFPA_WG_LAUNCH(1, 16, Q);                        \
     } while (0)
     if (d->precision == 3 && d->mode == 0) {
       // wgrad_bf16_kernel: 128-channel output tiles when C_out allows; as few patch groups as give every CU one workgroup (the atomics
@@ -1978,7 +1976,7 @@ int mfpa_wgrad_mfma(const mfpa_wgrad_desc* d, void* stream) {
       const int cot = d->Cout % 128 == 0 ? 4 : 2;
       const int tiles2 = (d->Cout / (32 * cot)) * ((d->C0 + d->C1) / WG_T);
       const int cus = mfpa_current_device_cus();
-      const int target = MFPA_EXP_ENV("MFPA_WGRAD_WGS", cus > 0 ? cus : 256);
+      const int target = cus > 0 ? cus : 256;
       long long split2 = (target + tiles2 - 1) / tiles2;
       if (split2 > npatch_b) split2 = npatch_b;
       if (split2 < 1) split2 = 1;
@@ -1990,8 +1988,7 @@ int mfpa_wgrad_mfma(const mfpa_wgrad_desc* d, void* stream) {
       else if (pw == 32) hipLaunchKernelGGL((wgrad_bf16_kernel<32, 2>), grid2, dim3(512), lds2, s, a);
       else hipLaunchKernelGGL((wgrad_bf16_kernel<16, 2>), grid2, dim3(512), lds2, s, a);
     } else if (d->precision == 3) {
-      static const int ci128_env = MFPA_EXP_ENV("MFPA_WGRAD_T_CI128", 1);
-      if (ci128_env && d->C0 % 128 == 0 && d->C1 == 0) {
+      if (d->C0 % 128 == 0 && d->C1 == 0) {
         // 64 output x 128 input channels per workgroup (halves the re-reads of the four dz tap tiles)
         const int tiles3 = (d->Cout / WG_T) * (d->C0 / 128);
         long long split3 = (1024 + tiles3 - 1) / tiles3;
@@ -2005,10 +2002,8 @@ int mfpa_wgrad_mfma(const mfpa_wgrad_desc* d, void* stream) {
       } else if (pw == 32) hipLaunchKernelGGL((wgrad_bf16x3_kernel<1, 32, 8, true, true>), grid, dim3(512), lds, s, a);
       else hipLaunchKernelGGL((wgrad_bf16x3_kernel<1, 16, 8, true, true>), grid, dim3(512), lds, s, a);
     }
-    else if (nw == 8 && plain) MFPA_WG_PICK(8, true);
-    else if (nw == 8) MFPA_WG_PICK(8, false);
-    else if (plain) MFPA_WG_PICK(4, true);
-    else MFPA_WG_PICK(4, false);
+    else if (plain) MFPA_WG_PICK(true);
+    else MFPA_WG_PICK(false);
 #undef MFPA_WG_PICK
 #undef MFPA_WG_LAUNCH
   } else if (d->mode == 0) {

@@ -21,55 +21,19 @@
 // (ty, tx) "pairs" -- the two column phases of a pair are the two halves of what a tap is in the skip half, each half with its own
 // weight fragments (the wave's row phase and the half's column phase pick the composite), a ring of two pairs of register sets.
 #include "mfpa_common.h"
+#include "mfpa_conv_tile.h"
 #include "mfpa_unet_args.h"
-
-#include <type_traits>
 
 namespace mfpa_unet {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+using namespace mfpa_tile;
+using namespace mfpa_tile::role_split;     // tile geometry and LDS plane layout (shared with conv_ws64_kernel); PT's group index here: 4 * px + j (column parity, row pair)
 
-constexpr int KC = 32;                                                 // channels per K chunk
-constexpr int PH = 8, PW = 32, HPW = PW + 2, HPH = PH + 2, HP = HPW * HPH;   // the skip's halo patch: 10 x 34
 constexpr int HALF = HPW / 2;                                          // a staged halo row: 17 even halo columns, then the 17 odd ones
 constexpr int LPH = PH / 2 + 2, LPW = PW / 2 + 2, LP = LPH * LPW;      // the low-resolution patch: 6 x 18
-constexpr int THREADS = 512, LTHREADS = 256;
-constexpr int SPP = KC / 4;                                            // staging slots (16 B = 4 fp32 channels) per pixel and chunk
-constexpr int PPI = LTHREADS / SPP;                                    // pixels per loader pass
-constexpr int A_F4 = (HP + PPI - 1) / PPI;                             // staging slots per loader thread and skip chunk (11)
-constexpr int L_F4 = (LP + PPI - 1) / PPI;                             // ... and low-resolution chunk (4)
-constexpr int HPS = A_F4 * PPI;
-constexpr int PLANE = ((HPS * 16 + 255) / 256) * 256;                  // bytes of one (hi | lo, k-group) plane
-constexpr int HLS = 4 * PLANE + 256;                                   // hi -> lo distance (planes 2, 3 sit 128 B further)
-constexpr int STAGE = 2 * HLS;
-constexpr int PT = 8;                                                  // 16-pixel groups per compute wave: index 4 * px + j (column parity, row pair)
+constexpr int L_F4 = (LP + PPI - 1) / PPI;                             // staging slots per loader thread and low-resolution chunk (4; skip chunk: A_F4)
 constexpr int EPI_FLOATS = 64 + 16 * 64;                               // [shift 64 | bias table 4 x 4 x 64]
-constexpr int OUTBUF = PH * PW * 64 * 4;                                // the epilogue's LDS tile (see conv_ws64_kernel)
-
-__device__ __forceinline__ constexpr int plane_off(int hl, int kg) { return hl * HLS + kg * PLANE + (kg >> 1) * 128; }
-
-template <int SLOTS, int LEFT, int I = 0>
-__device__ __forceinline__ void pin_reads() {
-  if constexpr (I < SLOTS && LEFT > 0) {
-    constexpr int k = (LEFT + (SLOTS - I) - 1) / (SLOTS - I);
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, k, 0);
-    pin_reads<SLOTS, LEFT - k, I + 1>();
-  }
-}
-constexpr int pin_read_slots(int slots, int left) {
-  int used = 0;
-  for (int i = 0; i < slots && left > 0; ++i) {
-    left -= (left + (slots - i) - 1) / (slots - i);
-    ++used;
-  }
-  return used;
-}
 
 __device__ __forceinline__ int tile_of(int b, int i, int G, int ngrp) {
   // one channel group: walkers b and b + 8 share an XCD, and the 32 walkers of an XCD take consecutive tiles (their shared halo rows meet in its L2);
@@ -220,47 +184,23 @@ __global__ __launch_bounds__(THREADS, 1) void conv_up_kernel(UpArgs a) {
       }
       unsigned hi[2], lo[2];
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const f32x2 x = {v[2 * h], v[2 * h + 1]};
-        hi[h] = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
-        const f32x2 r = {x[0] - __uint_as_float(hi[h] << 16), x[1] - __uint_as_float(hi[h] & 0xffff0000u)};
-        lo[h] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-      }
+      for (int h = 0; h < 2; ++h) split_bf16x3(f32x2{v[2 * h], v[2 * h + 1]}, hi[h], lo[h]);
       char* at = wbase + stage_off + it * PPI * 16;
       *reinterpret_cast<uint2*>(at) = uint2{hi[0], hi[1]};
       *reinterpret_cast<uint2*>(at + HLS) = uint2{lo[0], lo[1]};
     };
-    static_assert(A_F4 == 11 && L_F4 == 4, "eleven / four staging slots per loader thread");
-#define MFPA_UP_EACH4(M) M(0) M(1) M(2) M(3)
-#define MFPA_UP_EACH7(M) M(4) M(5) M(6) M(7) M(8) M(9) M(10)
     auto issue_all = [&](const Src& S, unsigned ain, auto SET) __attribute__((always_inline)) {
       if (S.from0) {
-        if (S.interior) {
-#define MFPA_UP_ISSUE(I) issue_slot(S, ain, off0[I], std::true_type{}, SET, std::integral_constant<int, I>{});
-          MFPA_UP_EACH4(MFPA_UP_ISSUE) MFPA_UP_EACH7(MFPA_UP_ISSUE)
-#undef MFPA_UP_ISSUE
-        } else {
-#define MFPA_UP_ISSUE(I) issue_slot(S, ain, off0[I], std::false_type{}, SET, std::integral_constant<int, I>{});
-          MFPA_UP_EACH4(MFPA_UP_ISSUE) MFPA_UP_EACH7(MFPA_UP_ISSUE)
-#undef MFPA_UP_ISSUE
-        }
+        if (S.interior) each_index<A_F4>([&](auto IT) __attribute__((always_inline)) { issue_slot(S, ain, off0[decltype(IT)::value], std::true_type{}, SET, IT); });
+        else each_index<A_F4>([&](auto IT) __attribute__((always_inline)) { issue_slot(S, ain, off0[decltype(IT)::value], std::false_type{}, SET, IT); });
       } else {
-        if (S.interior) {
-#define MFPA_UP_ISSUE(I) issue_slot(S, ain, off1[I], std::true_type{}, SET, std::integral_constant<int, I>{});
-          MFPA_UP_EACH4(MFPA_UP_ISSUE)
-#undef MFPA_UP_ISSUE
-        } else {
-#define MFPA_UP_ISSUE(I) issue_slot(S, ain, off1[I], std::false_type{}, SET, std::integral_constant<int, I>{});
-          MFPA_UP_EACH4(MFPA_UP_ISSUE)
-#undef MFPA_UP_ISSUE
-        }
+        if (S.interior) each_index<L_F4>([&](auto IT) __attribute__((always_inline)) { issue_slot(S, ain, off1[decltype(IT)::value], std::true_type{}, SET, IT); });
+        else each_index<L_F4>([&](auto IT) __attribute__((always_inline)) { issue_slot(S, ain, off1[decltype(IT)::value], std::false_type{}, SET, IT); });
       }
     };
     auto split_all = [&](auto SET, int stage_off, bool from0) __attribute__((always_inline)) {
-#define MFPA_UP_SPLIT(I) split_slot(SET, std::integral_constant<int, I>{}, stage_off);
-      MFPA_UP_EACH4(MFPA_UP_SPLIT)
-      if (from0) { MFPA_UP_EACH7(MFPA_UP_SPLIT) }
-#undef MFPA_UP_SPLIT
+      each_index<L_F4>([&](auto IT) __attribute__((always_inline)) { split_slot(SET, IT, stage_off); });
+      if (from0) each_index<A_F4 - L_F4, L_F4>([&](auto IT) __attribute__((always_inline)) { split_slot(SET, IT, stage_off); });
     };
     // the chunk sequence of this workgroup: (tile i, chunk c), c fastest: the skip's chunks, then the low-resolution tensor's
     int qi = 0, qc = 0;
@@ -320,18 +260,13 @@ __global__ __launch_bounds__(THREADS, 1) void conv_up_kernel(UpArgs a) {
     wq[slot][1][0] = __builtin_bit_cast(frag_t, __builtin_amdgcn_raw_buffer_load_b128(rs, wlane + 2048, so, 0));
     wq[slot][1][1] = __builtin_bit_cast(frag_t, __builtin_amdgcn_raw_buffer_load_b128(rs, wlane + 3072, so, 0));
   };
-#ifdef MFPA_UP_WHOT            // timing-only variant (tools/: wrong results by design): every weight fragment comes from ONE block per wave, i.e. from L1
-#define MFPA_UP_WBLK(x) (wcol)
-#else
-#define MFPA_UP_WBLK(x) (x)
-#endif
   auto load_w_skip = [&](int chunk, int tap, auto SLOT) __attribute__((always_inline)) {
-    load_w_at(rs_skip, MFPA_UP_WBLK(((unsigned)tap * (unsigned)nsk + (unsigned)chunk) * wrow + wcol), SLOT);
+    load_w_at(rs_skip, ((unsigned)tap * (unsigned)nsk + (unsigned)chunk) * wrow + wcol, SLOT);
   };
   // composite image: "tap" index ((py * 2 + px) * 2 + ty) * 2 + tx, py = this wave's row parity
   auto load_w_up = [&](int chunk, int pair, int px, auto SLOT) __attribute__((always_inline)) {
     const unsigned t16 = (unsigned)((wm * 2 + px) * 4 + pair);
-    load_w_at(rs_up, MFPA_UP_WBLK((t16 * (unsigned)nup + (unsigned)chunk) * wrow + wcol), SLOT);
+    load_w_at(rs_up, (t16 * (unsigned)nup + (unsigned)chunk) * wrow + wcol, SLOT);
   };
   struct XFrags { frag_t h[4], l[4]; };                                 // PREC 0: h = piece 2 g, l = piece 2 g + 1
   XFrags fx0, fx1;

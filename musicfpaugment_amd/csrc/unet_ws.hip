@@ -24,105 +24,23 @@
 // LDS: two stages of eight planes [hi | lo][k-group] of (pixel x 16 B), the layout conv_wd16_kernel reads (conflict-free ds_read_b128).
 // Same products and the same summation inside an instruction as conv_wd16_kernel: bit-identical outputs (tests/test_gpu_unet.py).
 #include "mfpa_common.h"
+#include "mfpa_conv_tile.h"
 #include "mfpa_unet_args.h"
 
-#include <type_traits>
-
 namespace mfpa_unet {
-#if defined(MFPA_EXPERIMENTS) || defined(MFPA_WS_STAMPS)
-__device__ unsigned long long* ws_stamps = nullptr;
-#endif
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+using namespace mfpa_tile;
+using namespace mfpa_tile::role_split;     // tile geometry and LDS plane layout (shared with conv_up_kernel)
 
-#ifndef MFPA_WS_COMPUTE_PRIO
-#define MFPA_WS_COMPUTE_PRIO 0     // s_setprio of the compute waves (A/B builds)
-#endif
-#ifndef MFPA_WS_LOADER_PRIO
-#define MFPA_WS_LOADER_PRIO 0      // s_setprio of the loader waves: their few hundred instructions per chunk go first, then they sleep at the barrier
-                                   // (at equal priority the older compute wave of the SIMD wins every arbitration and a loader turn took
-                                   //  7.7 k cycles of a 9.4 k-cycle chunk: the compute waves waited for it at the barrier)
-#endif
-#ifndef MFPA_WS_EPI_PRIO
-#define MFPA_WS_EPI_PRIO 0         // s_setprio of a compute wave inside its epilogue (its ~200 vector instructions would otherwise queue behind the loader's turn)
-#endif
-#ifndef MFPA_WS_SYNC
-#define MFPA_WS_SYNC 0             // 1: stages and the epilogue's tile are handed over through four LDS counters (no s_barrier in the loop: a wave waits only
-                                   //    for the data it needs, and normally finds it there); 0: one s_barrier per chunk for all eight waves (A/B builds)
-#endif
-#ifndef MFPA_WS_PACE
-#define MFPA_WS_PACE 0             // s_sleep units (64 cycles) a loader wave waits behind EACH halo request: the CU's vector-memory path serves all waves
-                                   // in order, so a burst of 44 KB of HBM requests holds up the compute waves' weight fragments (L2 hits) behind it
-#endif
-#ifndef MFPA_WS_XCD_TILES
-#define MFPA_WS_XCD_TILES 1        // the 32 workgroups of an XCD walk 32 CONSECUTIVE tiles at a time (their shared halo rows meet in that XCD's L2)
-#endif
-
-// timing-only variants (tools/build_ws_variants.py: -DMFPA_SKIP_BITS=<bits>, compile-time, wrong results by design) and the in-kernel
-// timeline (-DMFPA_WS_STAMPS or the experiments build): the product build contains neither
-#ifdef MFPA_SKIP_BITS
-#define WS_FLAG(bit) (((MFPA_SKIP_BITS) & (bit)) != 0)
-#else
-#define WS_FLAG(bit) false
-#endif
-#if defined(MFPA_EXPERIMENTS) && !defined(MFPA_WS_STAMPS)
-#define MFPA_WS_STAMPS 1
-#endif
-#ifdef MFPA_WS_STAMPS
-// In-kernel timeline (experiments build only; tools/exp_ws_timeline.py): wave 0 (compute) and wave 4 (loader) of workgroup 17 stamp s_memtime
-// into LDS (tag in the low 8 bits), dumped to this buffer when the kernel ends: [0] = count of wave 0, [1 ..] its stamps; [2048] = count of
-// wave 4, [2049 ..] its stamps.  No output value depends on a stamp.  (the symbol: mfpa_unet::ws_stamps above)
-constexpr int WS_MAX_STAMPS = 128;
-#endif
-
-constexpr int KC = 32;             // channels per K chunk
-constexpr int PH = 8, PW = 32, HPW = PW + 2, HPH = PH + 2, HP = HPW * HPH;
-constexpr int THREADS = 512, LTHREADS = 256;
-constexpr int SPP = KC / 4;                                            // staging slots (16 B = 4 fp32 channels) per pixel and chunk
-constexpr int PPI = LTHREADS / SPP;                                    // pixels per loader pass
-constexpr int A_F4 = (HP + PPI - 1) / PPI;                             // staging slots per loader thread and chunk (11)
-constexpr int HPS = A_F4 * PPI;                                        // staged pixels (>= HP)
-constexpr int PLANE = ((HPS * 16 + 255) / 256) * 256;                  // bytes of one (hi | lo, k-group) plane, a multiple of 256
-constexpr int HLS = 4 * PLANE + 256;                                   // hi -> lo distance (planes 2, 3 sit 128 B further)
-constexpr int STAGE = 2 * HLS;
-constexpr int TAPS = 9, PT = 8;                                        // 16-pixel tiles per compute wave
-constexpr int OUTBUF = PH * PW * 64 * 4;                                // the epilogue's LDS tile: 256 px x 64 ch fp32, piece (pixel m, channel quad q) at m * 256 + ((q ^ (m & 15)) << 4)
+constexpr int TAPS = 9;
 constexpr int C1W = PW + 4, C1PROWS = 6;                               // C1SRC: a loader wave's part of the 1-channel source patch: <= 6 rows of PW + 4 columns
 constexpr int C1LDS = (4 * C1PROWS * C1W + 128) * 4;                   // four wave-private patches + the first layer's (scale 64, shift 64)
-
-__device__ __forceinline__ constexpr int plane_off(int hl, int kg) { return hl * HLS + kg * PLANE + (kg >> 1) * 128; }
-
-// sched_group_barrier pattern "one MFMA, then k LDS reads" with LEFT reads spread evenly over SLOTS MFMAs
-template <int SLOTS, int LEFT, int I = 0>
-__device__ __forceinline__ void pin_reads() {
-  if constexpr (I < SLOTS && LEFT > 0) {
-    constexpr int k = (LEFT + (SLOTS - I) - 1) / (SLOTS - I);
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, k, 0);
-    pin_reads<SLOTS, LEFT - k, I + 1>();
-  }
-}
-constexpr int pin_read_slots(int slots, int left) {
-  int used = 0;
-  for (int i = 0; i < slots && left > 0; ++i) {
-    left -= (left + (slots - i) - 1) / (slots - i);
-    ++used;
-  }
-  return used;
-}
 
 // tile index of workgroup b's i-th tile.  Plain: b + i G.  XCD-aware: workgroups b and b + 8 share an XCD (round-robin dispatch: speed
 // only), so within a round of G tiles XCD x = b % 8 takes the G / 8 consecutive tiles [x G / 8, (x + 1) G / 8).
 __device__ __forceinline__ int tile_of(int b, int i, int G) {
-#if MFPA_WS_XCD_TILES
   if ((G & 7) == 0) return i * G + (b & 7) * (G >> 3) + (b >> 3);
-#endif
   return i * G + b;
 }
 
@@ -142,11 +60,8 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
   const int first_tile = tile_of((int)blockIdx.x, 0, G);
   const int owned = first_tile < ntiles ? (ntiles - first_tile + G - 1) / G : 0;
 
-  // LDS: [stage 0 | stage 1 | epilogue constants: scale 64, shift 64, w1x1 64, accumulator start values 64 | the epilogue's output tile 64 KB | (stamps)]
+  // LDS: [stage 0 | stage 1 | epilogue constants: scale 64, shift 64, w1x1 64, accumulator start values 64 | the epilogue's output tile 64 KB]
   float* const epi = reinterpret_cast<float*>(smem + 2 * STAGE);
-#if MFPA_WS_SYNC
-  unsigned* const syncw = reinterpret_cast<unsigned*>(epi + 256);      // 4 x 4 progress words
-#endif
   char* const outbuf = smem + 2 * STAGE + (256 + 16) * sizeof(float);
   float* const c1s = reinterpret_cast<float*>(outbuf + OUTBUF);        // C1SRC: [4 wave-private patches | scale 64 | shift 64]
   for (int i = tid; i < 64; i += THREADS) {
@@ -162,65 +77,10 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
     }
   }
 
-#ifdef MFPA_WS_STAMPS
-  unsigned long long* const tsbuf = reinterpret_cast<unsigned long long*>(smem + a.dbg_lds_stamps) + (wave >= 4 ? WS_MAX_STAMPS : 0);
-  int stamp_n = 0;
-  const bool stamping = ws_stamps != nullptr && a.dbg_lds_stamps != 0 && blockIdx.x == 17 && blockIdx.y == 0 && (tid == 0 || tid == LTHREADS);
-  auto stamp = [&](int tag) __attribute__((always_inline)) {
-    if (stamping && stamp_n < WS_MAX_STAMPS) tsbuf[stamp_n++] = (__builtin_amdgcn_s_memtime() & ~0xffull) | (unsigned)tag;
-  };
-  // the clock the chip holds inside this kernel (MI355X_MICROARCH.md, DVFS give-back item 6): every workgroup's first compute wave writes
-  // {d s_memtime (shader clock), d s_memrealtime (100 MHz)} over its whole life to ws_stamps[3000 + 2 * workgroup]
-  const unsigned long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-  auto dump_stamps = [&]() __attribute__((always_inline)) {
-    if (ws_stamps != nullptr && tid == 0 && blockIdx.y == 0 && blockIdx.x < 256) {
-      ws_stamps[3000 + 2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - clk_t0;
-      ws_stamps[3001 + 2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime() - clk_r0;
-    }
-    if (stamping) {
-      unsigned long long* out = ws_stamps + (wave >= 4 ? 2048 : 0);
-      for (int i = 0; i < stamp_n; ++i) out[1 + i] = tsbuf[i];
-      out[0] = stamp_n;
-    }
-  };
-#else
-  auto stamp = [](int) {};
-  auto dump_stamps = []() {};
-#endif
-#if MFPA_WS_SYNC
-  // Hand-offs through LDS words, four per kind: [READY | FREED | OUT_READY | OUT_FREE][wave of the role].  A wave publishes ITS OWN progress
-  // (how many chunks it has staged / left, how many output tiles it has written / stored) with a plain store into its word; a waiter reads
-  // the four words of a kind as one 16-byte piece and takes the minimum -- every wave of the other role must have got there (a summed
-  // counter is not enough: without the barrier the waves of a role drift up to a chunk apart, and three waves a chunk ahead would
-  // outvote a late one).  A wave's DS instructions execute in issue order, so "my accesses, then my word" needs no wait on the
-  // publishing side and "my poll has returned, then my accesses" none on the waiting side; hipcc must keep that program order (the empty
-  // asm statements).  Every spin is bounded: a protocol error must end in wrong numbers that a test catches, never in a hung GPU.
-  if (tid < 16) syncw[tid] = 0;
-  __syncthreads();                                                     // the kernel's only barrier: constants and progress words are in LDS
-  constexpr int READY = 0, FREED = 1, OUT_READY = 2, OUT_FREE = 3;
-  const int role_wave = wave & 3;
-  auto publish = [&](int which, unsigned count) __attribute__((always_inline)) {
-    asm volatile("" ::: "memory");
-    if (lane == 0) __hip_atomic_store(syncw + 4 * which + role_wave, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    asm volatile("" ::: "memory");
-  };
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  auto peek = [&](int which) __attribute__((always_inline)) {        // the slowest wave's progress
-    const u32x4 v = *reinterpret_cast<volatile u32x4*>(syncw + 4 * which);
-    return min(min(v[0], v[1]), min(v[2], v[3]));
-  };
-  auto wait_for = [&](int which, unsigned target) __attribute__((always_inline)) {
-    asm volatile("" ::: "memory");
-    int spins = 0;
-    while ((unsigned)__builtin_amdgcn_readfirstlane((int)peek(which)) < target && ++spins < (1 << 18)) __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-  };
-#endif
   if (wave >= 4) {
     // =================================================================================================== LOADER waves
-#if MFPA_WS_LOADER_PRIO
-    __builtin_amdgcn_s_setprio(MFPA_WS_LOADER_PRIO);
-#endif
+    // (tried in round 5, code retired: s_setprio for either role and in the epilogue, an s_sleep behind each halo request -- neither moved the
+    //  kernel; DESIGN.md section 7, NOTES round 5)
     const int lt = tid - LTHREADS;
     const int aq = lt % SPP;
     struct Tile { int b, y0, x0; unsigned ain; unsigned t0, t1; bool interior; };   // t0 / t1: byte offset of the tile's HALO origin (pixel (-1, -1)) in source 0 / 1: may wrap
@@ -287,12 +147,8 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
-              for (int e = 0; e < 2; ++e) {
-                const f32x2 x = {v[u][h][2 * e], v[u][h][2 * e + 1]};
-                hi[2 * h + e] = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
-                const f32x2 r = {x[0] - __uint_as_float(hi[2 * h + e] << 16), x[1] - __uint_as_float(hi[2 * h + e] & 0xffff0000u)};
-                lo[2 * h + e] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-              }
+              for (int e = 0; e < 2; ++e)
+                split_bf16x3(f32x2{v[u][h][2 * e], v[u][h][2 * e + 1]}, hi[2 * h + e], lo[2 * h + e]);
             if (gy < a.H && gx < a.W) {
               char* yp = yb + ((unsigned)gy * (unsigned)a.W + (unsigned)gx) * (unsigned)a.Cout * 4u + (unsigned)(kg8 >> 2) * 128u + (unsigned)(kg8 & 3) * 16u;
               *reinterpret_cast<uint4*>(yp) = uint4{hi[0], hi[1], hi[2], hi[3]};
@@ -380,82 +236,47 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
                                                                        // array base: both arrays went to scratch, a scratch load in front of every halo load)
         const bool inside = (ain >> (S.ainsh + it)) & 1u;
         const unsigned off = inside ? (S.from0 ? o0 : o1) + S.toff : 0xfffffff0u;
-        if (WS_FLAG(1) || WS_FLAG(32)) return;
         areg[set][it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(S.rs, (int)off, 0, 0));
-        if (MFPA_WS_PACE) __builtin_amdgcn_s_sleep(MFPA_WS_PACE);
       };
       // interior tiles (no slot to zero): the table entry is the vector offset as it stands, the tile / channel offset rides in the
       // instruction's scalar offset -- no vector instruction at all per request
       auto issue_slot_interior = [&](const Src& S, auto FROM0, auto SET, auto IT) __attribute__((always_inline)) {
         constexpr int it = decltype(IT)::value, set = decltype(SET)::value;
-        if (WS_FLAG(1) || WS_FLAG(32)) return;
         areg[set][it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(S.rs, (int)(decltype(FROM0)::value ? off0[it] : off1[it]), (int)S.toff, 0));
-        if (MFPA_WS_PACE) __builtin_amdgcn_s_sleep(MFPA_WS_PACE);
       };
-      // one staging slot: bf16 hi / lo split, two 8-byte stores into the (hi, k-group) and (lo, k-group) planes.  Per channel pair: one
-      // packed conversion, the two hi values back as floats by a shift and a mask, two subtractions, one packed conversion.
+      // one staging slot: bf16 hi / lo split, two 8-byte stores into the (hi, k-group) and (lo, k-group) planes
       char* const wbase = smem + plane_off(0, aq >> 1) + (lt / SPP) * 16 + 8 * (aq & 1);
       // (a source in the SPLIT layout -- mfpa_conv_desc.x0_split / x1_split -- needs none of this: its 16 bytes at the very same offset ARE
       //  the (hi | lo, k-group) piece aq = 4 hl + kg of the pixel: one 16-byte store)
       char* const wbase_split = smem + plane_off(aq >> 2, aq & 3) + (lt / SPP) * 16;
       auto copy_slot = [&](auto SET, auto IT, int stage_off) __attribute__((always_inline)) {
         constexpr int it = decltype(IT)::value, set = decltype(SET)::value;
-        if (WS_FLAG(1)) return;
         *reinterpret_cast<f32x4*>(wbase_split + stage_off + it * PPI * 16) = areg[set][it];
       };
       auto split_slot = [&](auto SET, auto IT, int stage_off) __attribute__((always_inline)) {
         constexpr int it = decltype(IT)::value, set = decltype(SET)::value;
-        if (WS_FLAG(1)) return;
         const f32x4 v = areg[set][it];
         unsigned hi[2], lo[2];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const f32x2 x = {v[2 * h], v[2 * h + 1]};
-          hi[h] = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
-          const f32x2 r = {x[0] - __uint_as_float(hi[h] << 16), x[1] - __uint_as_float(hi[h] & 0xffff0000u)};
-          lo[h] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-        }
+        for (int h = 0; h < 2; ++h) split_bf16x3(f32x2{v[2 * h], v[2 * h + 1]}, hi[h], lo[h]);
         char* at = wbase + stage_off + it * PPI * 16;
-        if (WS_FLAG(64)) {                                             // (timing variants: the split stays live, nothing is stored)
-          if (hi[0] + hi[1] + lo[0] + lo[1] == 0x12345678u) *reinterpret_cast<uint2*>(at) = uint2{hi[0], hi[1]};
-          return;
-        }
         *reinterpret_cast<uint2*>(at) = uint2{hi[0], hi[1]};
         *reinterpret_cast<uint2*>(at + HLS) = uint2{lo[0], lo[1]};
       };
-      static_assert(A_F4 == 11, "eleven staging slots per loader thread");
       auto issue_all = [&](const Src& S, unsigned ain, bool interior, auto SET) __attribute__((always_inline)) {
         if (interior) {
-          if (S.from0) {
-#define MFPA_WS_ISSUE(I) issue_slot_interior(S, std::true_type{}, SET, std::integral_constant<int, I>{});
-            MFPA_WS_ISSUE(0) MFPA_WS_ISSUE(1) MFPA_WS_ISSUE(2) MFPA_WS_ISSUE(3) MFPA_WS_ISSUE(4) MFPA_WS_ISSUE(5)
-            MFPA_WS_ISSUE(6) MFPA_WS_ISSUE(7) MFPA_WS_ISSUE(8) MFPA_WS_ISSUE(9) MFPA_WS_ISSUE(10)
-#undef MFPA_WS_ISSUE
-          } else {
-#define MFPA_WS_ISSUE(I) issue_slot_interior(S, std::false_type{}, SET, std::integral_constant<int, I>{});
-            MFPA_WS_ISSUE(0) MFPA_WS_ISSUE(1) MFPA_WS_ISSUE(2) MFPA_WS_ISSUE(3) MFPA_WS_ISSUE(4) MFPA_WS_ISSUE(5)
-            MFPA_WS_ISSUE(6) MFPA_WS_ISSUE(7) MFPA_WS_ISSUE(8) MFPA_WS_ISSUE(9) MFPA_WS_ISSUE(10)
-#undef MFPA_WS_ISSUE
-          }
+          if (S.from0) each_index<A_F4>([&](auto IT) __attribute__((always_inline)) { issue_slot_interior(S, std::true_type{}, SET, IT); });
+          else each_index<A_F4>([&](auto IT) __attribute__((always_inline)) { issue_slot_interior(S, std::false_type{}, SET, IT); });
           return;
         }
-#define MFPA_WS_ISSUE(I) issue_slot(S, ain, SET, std::integral_constant<int, I>{});
-        MFPA_WS_ISSUE(0) MFPA_WS_ISSUE(1) MFPA_WS_ISSUE(2) MFPA_WS_ISSUE(3) MFPA_WS_ISSUE(4) MFPA_WS_ISSUE(5)
-        MFPA_WS_ISSUE(6) MFPA_WS_ISSUE(7) MFPA_WS_ISSUE(8) MFPA_WS_ISSUE(9) MFPA_WS_ISSUE(10)
-#undef MFPA_WS_ISSUE
+        each_index<A_F4>([&](auto IT) __attribute__((always_inline)) { issue_slot(S, ain, SET, IT); });
       };
       auto split_all = [&](auto SET, int stage_off, bool src_split) __attribute__((always_inline)) {
         if (src_split) {
-#define MFPA_WS_COPY(I) copy_slot(SET, std::integral_constant<int, I>{}, stage_off);
-          MFPA_WS_COPY(0) stamp(21); MFPA_WS_COPY(1) MFPA_WS_COPY(2) MFPA_WS_COPY(3) MFPA_WS_COPY(4) MFPA_WS_COPY(5)
-          MFPA_WS_COPY(6) MFPA_WS_COPY(7) MFPA_WS_COPY(8) MFPA_WS_COPY(9) MFPA_WS_COPY(10)
-#undef MFPA_WS_COPY
+          each_index<A_F4>([&](auto IT) __attribute__((always_inline)) { copy_slot(SET, IT, stage_off); });
           return;
         }
-#define MFPA_WS_SPLIT(I) split_slot(SET, std::integral_constant<int, I>{}, stage_off);
-        MFPA_WS_SPLIT(0) stamp(21); MFPA_WS_SPLIT(1) MFPA_WS_SPLIT(2) MFPA_WS_SPLIT(3) MFPA_WS_SPLIT(4) MFPA_WS_SPLIT(5)
-        MFPA_WS_SPLIT(6) MFPA_WS_SPLIT(7) MFPA_WS_SPLIT(8) MFPA_WS_SPLIT(9) MFPA_WS_SPLIT(10)
-#undef MFPA_WS_SPLIT
+        each_index<A_F4>([&](auto IT) __attribute__((always_inline)) { split_slot(SET, IT, stage_off); });
       };
       // the chunk sequence of this workgroup: (tile i, chunk c), c fastest.  Q = the next chunk to REQUEST.
       int qi = 0, qc = 0;
@@ -485,34 +306,11 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
         return (c0 < a.C0 ? a.x0_split : a.x1_split) != 0;
       };
       auto iteration = [&](int k, auto ISSUE_SET, auto SPLIT_SET) __attribute__((always_inline)) {
-        stamp(20);
         if (k + 2 < total) issue_next(ISSUE_SET);
         __builtin_amdgcn_sched_barrier(0);                             // the requests first: hipcc sank them below the split
-#if MFPA_WS_SYNC
-        // counters: chunk k + 1 goes into the stage chunk k - 1 was read from -- when all four compute waves have left it
-        if (k + 1 < total) {
-          if (k >= 1) wait_for(FREED, (unsigned)k);                    // every compute wave has left chunk k - 1
-          split_all(SPLIT_SET, par * STAGE, src_split_of(k + 1));
-          publish(READY, (unsigned)(k + 2));                           // this wave's part of chunks 0 .. k + 1 is staged
-        }
-        stamp(22);
-        // the output tile of tile i (last chunk k_i = (i + 1) nchunks - 1) is written by the compute waves right behind that chunk:
-        // stored here in iteration k_i + 1, behind this iteration's own chunk
-        if (has_duty && !WS_FLAG(4) && k >= nchunks && k % nchunks == 0) {
-          wait_for(OUT_READY, (unsigned)(k / nchunks));
-          duty(tile_of((int)blockIdx.x, k / nchunks - 1, G));
-          publish(OUT_FREE, (unsigned)(k / nchunks));                  // this wave has read its part of tiles 0 .. k / nchunks - 1
-        }
-        stamp(24);
-        stamp(23);
-#else
         if (k + 1 < total) split_all(SPLIT_SET, par * STAGE, src_split_of(k + 1));
-        stamp(22);
-        if (has_duty && !WS_FLAG(4) && k >= nchunks + 1 && (k - 1) % nchunks == 0) duty(tile_of((int)blockIdx.x, (k - 1) / nchunks - 1, G));
-        stamp(24);
+        if (has_duty && k >= nchunks + 1 && (k - 1) % nchunks == 0) duty(tile_of((int)blockIdx.x, (k - 1) / nchunks - 1, G));
         __syncthreads();                                               // k = -1: stage 0 is ready; k >= 0: the compute waves' barrier of chunk k
-        stamp(23);
-#endif
         par ^= 1;
       };
       for (int k = -1; k < total; k += 2) {
@@ -521,11 +319,7 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
       }
       if (has_duty) {
         // the last tile's read-out iteration lies beyond the loop (every other tile's does not: nchunks >= 2)
-#if MFPA_WS_SYNC
-        wait_for(OUT_READY, (unsigned)owned);
-#else
         __syncthreads();                                               // the compute waves' final barrier: the last tile's output is in LDS
-#endif
         duty(tile_of((int)blockIdx.x, owned - 1, G));
       }
     } else {
@@ -543,12 +337,8 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
       float* const patch = c1s + lw * (C1PROWS * C1W);
       const float* const c1c = c1s + 4 * C1PROWS * C1W;
       const int g = lane >> 4, p = lane & 15;
-      auto split2 = [&](float x0_, float x1_, unsigned& hi, unsigned& lo) __attribute__((always_inline)) {
-        const f32x2 x = {x0_, x1_};
-        hi = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
-        const f32x2 r = {x[0] - __uint_as_float(hi << 16), x[1] - __uint_as_float(hi & 0xffff0000u)};
-        lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-      };
+      // (a local wrapper on purpose: with split_bf16x3 called directly at the six sites hipcc allocates this kernel's registers differently)
+      auto split2 = [&](float x0_, float x1_, unsigned& hi, unsigned& lo) __attribute__((always_inline)) { split_bf16x3(f32x2{x0_, x1_}, hi, lo); };
       // the first layer's weights as the A operand: lane (g, c) = channel 16 t + c, k = 4 g .. 4 g + 3 (tap k, zero from tap 9 on)
       s16x4 Ahi[4], Alo[4];
 #pragma unroll
@@ -669,7 +459,6 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
       int par = 0;
       request_patch(tile_of((int)blockIdx.x, 0, G));
       for (int k = -1; k < total; ++k) {
-        stamp(20);
         if (k + 1 < total) {
           const int i = (k + 1) >> 1, c = (k + 1) & 1;
           if (c == 0) {
@@ -679,11 +468,8 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
           }
           produce(c, par * STAGE);
         }
-        stamp(22);
         if (has_duty && k >= 3 && (k - 1) % 2 == 0) duty(tile_of((int)blockIdx.x, (k - 1) / 2 - 1, G));
-        stamp(24);
         __syncthreads();
-        stamp(23);
         par ^= 1;
       }
       if (has_duty) {
@@ -691,22 +477,16 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
         duty(tile_of((int)blockIdx.x, owned - 1, G));
       }
     }
-    dump_stamps();
     return;
   }
 
   // ===================================================================================================== COMPUTE waves
-#if MFPA_WS_COMPUTE_PRIO
-  __builtin_amdgcn_s_setprio(MFPA_WS_COMPUTE_PRIO);
-#endif
   const int wm = wave & 1, wn = wave >> 1;                             // pixel half (rows 4 wm .. 4 wm + 3), channel half
   const int p = lane & 15, g = lane >> 4;
 
-  bool primed = false;
   bf16x8 wq[3][2][2];                                                  // weight fragments: ring of three sets, [slot][16-channel tile][hi, lo]
   auto load_w = [&](int chunk, int tap, auto SLOT) __attribute__((always_inline)) {
     constexpr int slot = decltype(SLOT)::value;
-    if (WS_FLAG(16) && primed) return;                    // (timing variants: the ring keeps the prologue's weights)
     const char* wb = reinterpret_cast<const char*>(a.w) + ((((size_t)tap * nchunks + chunk) * (size_t)(a.Cout / 16) + (size_t)(n0 / 16 + 2 * wn)) << 11) + lane * 16;
     wq[slot][0][0] = *reinterpret_cast<const bf16x8*>(wb);
     wq[slot][0][1] = *reinterpret_cast<const bf16x8*>(wb + 1024);
@@ -718,7 +498,6 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
   const int xbase = ((4 * wm) * HPW + p) * 16 + plane_off(0, g);      // the lane's row of pixel tile 0 in plane (hi, g) at tap (0, 0)
   auto tile_disp = [](int pt) { return ((pt >> 1) * HPW + (pt & 1) * 16) * 16; };
   auto read_x = [&](XFrags& f, const char* stage, int tap_off, int half) __attribute__((always_inline)) {
-    if (WS_FLAG(8)) return;                               // (timing variants: the fragments of the prologue's read stay in the registers)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const char* r = stage + xbase + tile_disp(4 * half + i) + tap_off;
@@ -756,10 +535,6 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
   // 4..7) || read tiles 0..3 of tap t + 1.  The chunk's one barrier sits between the phases of tap 8: behind it the other stage is complete
   // (the loaders arrived) and this one is read out (every compute wave's fragment reads of it have returned: lgkmcnt(0) in front of it).
   int kpar = 0;                                                        // parity of the stage the current chunk is read from
-#if MFPA_WS_SYNC
-  unsigned gck = 0, rdy_early = 0;                                     // this workgroup's chunk counter; the READY count peeked at tap 7
-  const unsigned total_c = (unsigned)(owned * nchunks);
-#endif
   auto tap_body = [&](auto TAP, int chunk, auto FIRST) __attribute__((always_inline)) {
     constexpr int tap = decltype(TAP)::value;
     constexpr int ntap = (tap + 1) % TAPS;
@@ -767,7 +542,6 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
     const int chunk_n = chunk + 1 < nchunks ? chunk + 1 : 0;
     const char* cur = smem + kpar * STAGE;
     const char* nxt = (tap == TAPS - 1) ? smem + (kpar ^ 1) * STAGE : cur;
-    stamp(tap);
     read_x(fx1, cur, tap_off, 1);
     mfma_half(fx0, wq[tap % 3], 0, FIRST);
     load_w((tap + 2 >= TAPS) ? chunk_n : chunk, (tap + 2) % TAPS, std::integral_constant<int, (tap + 2) % 3>{});
@@ -777,22 +551,10 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
     __builtin_amdgcn_sched_group_barrier(0x020, N_W, 0);
     if constexpr (N_M - used_a - 1 > 0) __builtin_amdgcn_sched_group_barrier(0x008, N_M - used_a - 1, 0);
     __builtin_amdgcn_sched_barrier(0);
-#if MFPA_WS_SYNC
-    if (tap == TAPS - 2) rdy_early = peek(READY);                      // the count the next tap checks, requested a tap ahead of its use
-#endif
     if (tap == TAPS - 1) {
-      stamp(9);
-#if MFPA_WS_SYNC
-      // this wave has issued its last read of the current stage: free it (the loaders wait for all four), then make sure the next stage
-      // is there -- the count read a tap ago normally says so already
-      publish(FREED, gck + 1u);
-      if (gck + 1u < total_c && (unsigned)__builtin_amdgcn_readfirstlane((int)rdy_early) < gck + 2u) wait_for(READY, gck + 2u);
-      ++gck;                                                             // (behind the workgroup's last chunk there is nothing to wait for)
-#else
-      __syncthreads();
-#endif
+      __syncthreads();                                                 // (tried instead in round 5, code retired: hand-offs through LDS progress counters
+                                                                       //  with no barrier in the loop -- did not move the kernel; DESIGN.md section 7, NOTES round 5)
       __builtin_amdgcn_sched_barrier(0);
-      stamp(10);
     }
     read_x(fx0, nxt, ntap_off, 0);
     mfma_half(fx1, wq[tap % 3], 1, FIRST);
@@ -803,19 +565,7 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
 
   load_w(0, 0, std::integral_constant<int, 0>{});
   load_w(0, 1, std::integral_constant<int, 1>{});
-  if (WS_FLAG(16)) { load_w(0, 2, std::integral_constant<int, 2>{}); primed = true; }
-#if MFPA_WS_SYNC
-  wait_for(READY, 1u);                                                 // stage 0 holds chunk 0 of the first tile
-#else
   __syncthreads();                                                     // stage 0 holds chunk 0 of the first tile
-#endif
-  if (WS_FLAG(8)) {                                       // timing variants: both fragment sets once
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      fx0.h[i] = fx1.h[i] = *reinterpret_cast<const bf16x8*>(smem + xbase + tile_disp(i));
-      fx0.l[i] = fx1.l[i] = *reinterpret_cast<const bf16x8*>(smem + xbase + tile_disp(i) + HLS);
-    }
-  }
   read_x(fx0, smem, 0, 0);
   for (int ti = 0; ti < owned; ++ti) {
     int bx = __builtin_amdgcn_readfirstlane(tile_of((int)blockIdx.x, ti, G));
@@ -831,32 +581,11 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
     // branch diamond across which hipcc spilled 62 registers
     auto chunk_body = [&](int chunk, auto FIRST) __attribute__((always_inline)) {
       tap_body(std::integral_constant<int, 0>{}, chunk, FIRST);
-      tap_body(std::integral_constant<int, 1>{}, chunk, std::false_type{});
-      tap_body(std::integral_constant<int, 2>{}, chunk, std::false_type{});
-      tap_body(std::integral_constant<int, 3>{}, chunk, std::false_type{});
-      tap_body(std::integral_constant<int, 4>{}, chunk, std::false_type{});
-      tap_body(std::integral_constant<int, 5>{}, chunk, std::false_type{});
-      tap_body(std::integral_constant<int, 6>{}, chunk, std::false_type{});
-      tap_body(std::integral_constant<int, 7>{}, chunk, std::false_type{});
-      tap_body(std::integral_constant<int, 8>{}, chunk, std::false_type{});
+      each_index<TAPS - 1, 1>([&](auto TAP) __attribute__((always_inline)) { tap_body(TAP, chunk, std::false_type{}); });
       kpar ^= 1;
     };
     chunk_body(0, std::true_type{});
     for (int chunk = 1; chunk < nchunks; ++chunk) chunk_body(chunk, std::false_type{});
-    stamp(11);
-#if MFPA_WS_EPI_PRIO
-    __builtin_amdgcn_s_setprio(MFPA_WS_EPI_PRIO);
-#endif
-    bool run_epi = true;
-    if (WS_FLAG(2)) {                                     // timing variants: no epilogue, but every accumulator stays live
-      float t = 0.f;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int pt = 0; pt < PT; ++pt) t += acc[ct][pt][0] + acc[ct][pt][1] + acc[ct][pt][2] + acc[ct][pt][3];
-      run_epi = t == 12345.678f;
-    }
-    if (run_epi) {
     // ---- epilogue: D[channel 4 g + j of tile ct][pixel p of tile pt]: out = relu(acc * scale + shift) -- or relu(acc) when the scale is in
     // the weights and the shift in the accumulators' start values.  ReLU as max(v, 0): NaN -> 0 like `v > 0 ? v : 0`; without ReLU nothing
     // touches the value (a NaN stays a NaN, as in the other kernels).
@@ -881,9 +610,6 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
           for (int j = 0; j < 4; ++j) acc[ct][pt][j] = fmaxf(acc[ct][pt][j], 0.f);
     }
     if (a.y != nullptr || a.w1x1 != nullptr) {
-#if MFPA_WS_SYNC
-      if (ti >= 1 && !WS_FLAG(4)) wait_for(OUT_FREE, (unsigned)ti);               // the loaders have stored the previous tile
-#endif
       // the tile goes to LDS as 16-byte pieces (pixel m, channel quad q) at m * 256 + ((q ^ (m & 15)) << 4): a wave instruction's 16 pixels
       // of one quad hit 16 different 16-byte bank groups; the loaders store it (and form the fused OutConv) one barrier from now
 #pragma unroll
@@ -899,9 +625,6 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
           *reinterpret_cast<f32x4*>(row + ((q ^ p) << 4)) = o;
         }
       }
-#if MFPA_WS_SYNC
-      publish(OUT_READY, (unsigned)(ti + 1));
-#endif
     }
     if (a.y_pool != nullptr) {
       // MaxPool2d(2) (floor): the window's two rows are two of the wave's pixel tiles, its two columns adjacent lanes (one DPP swap)
@@ -925,12 +648,7 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
               // split layout: channels 16 ct + 4 g .. + 3 of the chunk = half (g & 1) of k-group 2 ct + (g >> 1): 8 bytes of hi, 8 of lo
               unsigned hi[2], lo[2];
 #pragma unroll
-              for (int e = 0; e < 2; ++e) {
-                const f32x2 x = {v[2 * e], v[2 * e + 1]};
-                hi[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
-                const f32x2 r = {x[0] - __uint_as_float(hi[e] << 16), x[1] - __uint_as_float(hi[e] & 0xffff0000u)};
-                lo[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-              }
+              for (int e = 0; e < 2; ++e) split_bf16x3(f32x2{v[2 * e], v[2 * e + 1]}, hi[e], lo[e]);
               char* at = reinterpret_cast<char*>(pp) + (2 * ct + (g >> 1)) * 16 + 8 * (g & 1);
               *reinterpret_cast<uint2*>(at) = uint2{hi[0], hi[1]};
               *reinterpret_cast<uint2*>(at + 64) = uint2{lo[0], lo[1]};
@@ -940,16 +658,8 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
           }
         }
     }
-    }
-#if MFPA_WS_EPI_PRIO
-    __builtin_amdgcn_s_setprio(MFPA_WS_COMPUTE_PRIO);
-#endif
-    stamp(12);
   }
-#if !MFPA_WS_SYNC
   if (a.y != nullptr || a.w1x1 != nullptr) __syncthreads();          // the last tile's output is in LDS: the loaders store it
-#endif
-  dump_stamps();
 }
 
 }  // namespace
@@ -964,7 +674,7 @@ bool conv_ws64_serves(const ConvArgs& a) {
   // it must still lie beyond the clip, never inside it
   if (4ull * a.H * a.W * a.C0 + 4ull * (a.W + 2) * (unsigned long long)a.C0 * 2ull >= 0xfffffff0ull ||
       4ull * a.H1 * a.W1 * a.C1 + 4ull * (a.W1 + 2) * (unsigned long long)a.C1 * 2ull >= 0xfffffff0ull) return false;
-  if (c1 && (a.C0 != 64 || a.C1 != 0 || a.Cout != 64 || a.w1x1 != nullptr || !a.c1_w || !a.c1_scale || !a.c1_shift || MFPA_WS_SYNC)) return false;
+  if (c1 && (a.C0 != 64 || a.C1 != 0 || a.Cout != 64 || a.w1x1 != nullptr || !a.c1_w || !a.c1_scale || !a.c1_shift)) return false;
   const long long ntiles = (long long)((a.W + PW - 1) / PW) * ((a.H + PH - 1) / PH) * a.B;
   if (ntiles > 0x7fffffffLL / 2) return false;                         // (tile_of's round arithmetic stays inside 31 bits; conv_wd16_kernel takes those)
   return a.C0 % KC == 0 && a.C1 % KC == 0 && a.C0 + a.C1 >= 64;
@@ -978,10 +688,6 @@ int launch_conv_ws64(ConvArgs& a, hipStream_t s) {
   if (ntiles > 0x7fffffffLL / 2) return MFPA_EINVAL;
   const bool c1 = a.c1_x32 != nullptr || a.c1_spec64 != nullptr;
   const size_t lds = 2 * (size_t)STAGE + (256 + 16) * sizeof(float) + (size_t)OUTBUF + (c1 ? (size_t)C1LDS : 0);
-#ifdef MFPA_WS_STAMPS
-  a.dbg_lds_stamps = (int)lds;
-  const_cast<size_t&>(lds) += 2 * WS_MAX_STAMPS * sizeof(unsigned long long);
-#endif
   const int cus = mfpa_current_device_cus();
   const unsigned gy = (unsigned)(a.Cout / 64);
   unsigned gx = (unsigned)(cus > 0 ? cus : 256) / gy;
@@ -994,9 +700,3 @@ int launch_conv_ws64(ConvArgs& a, hipStream_t s) {
 }
 
 }  // namespace mfpa_unet
-
-#if defined(MFPA_EXPERIMENTS) || defined(MFPA_WS_STAMPS)
-extern "C" int mfpa_exp_ws_stamps(unsigned long long* buf) {      // experiments build only (not in include/mfpa.h)
-  return hipMemcpyToSymbol(HIP_SYMBOL(mfpa_unet::ws_stamps), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -181,3 +181,17 @@ def test_committed_build_record_matches_the_sources_in_the_tree():
         lib_h = hashlib.sha256(open(b.OUT, "rb").read()).hexdigest()
         assert local["sha256"] == lib_h, "libmfpa.so in the tree is not the build the record describes"
         assert local["sources_sha256"] == h.hexdigest(), "libmfpa.so in the tree was built from other sources: rebuild"
+
+
+def test_one_build_and_no_environment_reads(lib):
+    """There is one build of the library: no source under csrc/ reads the environment, build() takes no experiments switch, and the
+    library exports no experiment entry point."""
+    import inspect
+    from musicfpaugment_amd.csrc import build as b
+    for f in sorted(os.listdir(b.HERE)):
+        if f.endswith((".hip", ".h")):
+            assert "getenv" not in open(os.path.join(b.HERE, f)).read(), f
+    assert "experiments" not in inspect.signature(b.build).parameters
+    handle = ctypes.CDLL(lib.LIB_PATH)
+    with pytest.raises(AttributeError):
+        handle.mfpa_exp_ws_stamps

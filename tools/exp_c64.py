@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """The 64-channel full-resolution launches of the eval chain exactly as ops_unet.unet_forward_eval issues them (64 clips, 257 x 251):
 inc.3 (first layer in the loader + pool), up4.0 (skip 64 + up 64 -> 64, weights-direct persistent form), up4.3 (+ OutConv, no store),
-a plain 64 -> 64 with store, and the transposed convolution up4.up.  usage: exp_c64.py [--lib PATH] [--reps N]
-(experiments build + MFPA_CONV_DBG: skip experiments on conv_wd16_kernel<.., WMW = 4>)."""
+a plain 64 -> 64 with store, and the transposed convolution up4.up.  usage: exp_c64.py [--lib PATH] [--reps N]"""
 import argparse, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -41,7 +40,6 @@ runs = [("inc.3  c1src + pool", 64, lambda: K.conv3x3_fused(None, w64, sc, sh, p
         ("up4.3  + OutConv, no store", 64, lambda: K.conv3x3_fused(x, w64, sc, sh, precision=1, out1x1=(wo, 0.1), store=False, wf=wf64)),
         ("plain 64->64 with store", 64, lambda: K.conv3x3_fused(x, w64, sc, sh, precision=1, wf=wf64)),
         ("plain 64->64 + pool", 64, lambda: K.conv3x3_fused(x, w64, sc, sh, precision=1, pool=True, wf=wf64))]
-print("MFPA_CONV_DBG =", os.environ.get("MFPA_CONV_DBG", "0"))
 for name, ci, fn in runs:
     t = timed(fn)
     fl = 2.0 * B * H * W * ci * 64 * 9

@@ -651,6 +651,25 @@ typedef struct mfpa_gemm_desc {
   float* C2; long long ldc2, strideC2;
 } mfpa_gemm_desc;
 int mfpa_gemm_mfma(const mfpa_gemm_desc* d, void* stream);
+/* The kernel mfpa_gemm_mfma would launch for `d`, host arithmetic only (no device is touched, nothing is launched): MFPA_EINVAL
+ * exactly where mfpa_gemm_mfma returns it, otherwise MFPA_OK with *kernel_id (may be NULL) = one of the ids below;
+ * MFPA_GEMM_NONE for the no-ops batch == 0 / M == 0.  mfpa_gemm_mfma itself dispatches on this id. */
+enum {
+  MFPA_GEMM_NONE = -1,
+  MFPA_GEMM_PIPE = 0,          /* gemm_bf16x3_pipe_kernel<false>: 256 x 128 tile, K % 64 == 0, K >= 128, npad % 128 == 0, M >= 192 */
+  MFPA_GEMM_PIPE_WSPLIT = 1,   /* gemm_bf16x3_pipe_kernel<true>: the same on a pre-split W (precision 2) */
+  MFPA_GEMM_WIDE = 2,          /* gemm_bf16x3_wide_kernel<false>: 128 x 128 tile, K % 32 == 0, K >= 128, npad % 128 == 0 */
+  MFPA_GEMM_WIDE_WSPLIT = 3,   /* gemm_bf16x3_wide_kernel<true>: the same on a pre-split W (precision 2) */
+  MFPA_GEMM_BF16X3 = 4,        /* gemm_bf16x3_kernel: 128 x 64 tile, K % 32 == 0, K >= 128 */
+  MFPA_GEMM_SHORTK48_C1 = 5,   /* gemm_shortk_bf16x3_kernel<true, 48, 48>: K == 48, A computed from c1_x */
+  MFPA_GEMM_SHORTK48 = 6,      /* gemm_shortk_bf16x3_kernel<false, 48, 48>: K == 48 */
+  MFPA_GEMM_SHORTK96 = 7,      /* gemm_shortk_bf16x3_kernel<false, 96, 48>: K == 96 */
+  MFPA_GEMM_SMALLK48_C1 = 8,   /* gemm_smallk_kernel<true, 48>: fp32 products, K == 48, A computed from c1_x */
+  MFPA_GEMM_SMALLK48 = 9,      /* gemm_smallk_kernel<false, 48>: fp32 products, K == 48 */
+  MFPA_GEMM_MFMA_C1 = 10,      /* gemm_mfma_kernel<true>: fp32 products, any K % 16 == 0 up to 256, A computed from c1_x */
+  MFPA_GEMM_MFMA = 11          /* gemm_mfma_kernel<false>: fp32 products, any K % 16 == 0 */
+};
+int mfpa_gemm_mfma_route(const mfpa_gemm_desc* d, int* kernel_id);
 
 /* mix / (floor + std) zero-padded to VL samples, std = unbiased std over time (model.py:293-301). */
 int mfpa_demucs_prep(const float* wav, int B, int T, int VL, float floor_, float* out, float* stdv, void* stream);

@@ -21,7 +21,7 @@ EINVAL = -22
 EHIP = -1000
 F32, F64 = 0, 1
 STFT_TABLE_LEN = 1288
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 
 class MfpaError(RuntimeError):
@@ -86,6 +86,7 @@ _SIGNATURES = {
     "mfpa_upconv_pack": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_upconv_serves": ([c_int, c_int, c_int, c_int, c_int, c_int, c_int], c_int),
     "mfpa_gemm_mfma": ([c_void_p, c_void_p], c_int),
+    "mfpa_gemm_mfma_route": ([c_void_p, c_void_p], c_int),
     "mfpa_lowpass_taps": ([c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
     "mfpa_fir": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                   c_void_p, c_void_p], c_int),

@@ -1731,7 +1731,10 @@ extern "C" {
 #define SK_LDS(KCW) ((size_t)(GBM + GBN) * (4 * (KCW) + 16))
 constexpr int PIPE_MIN_M = 192;   // rows per clip from which the pipelined 256 x 128 kernel serves (rows past M are clamped when loaded: a 249-row clip fills 97 % of a 256-row tile)
 
-int mfpa_gemm_mfma(const mfpa_gemm_desc* d, void* stream) {
+// Validation and kernel choice of mfpa_gemm_mfma, host arithmetic only: MFPA_EINVAL, or MFPA_OK with *id = the MFPA_GEMM_* kernel that
+// serves `d` (MFPA_GEMM_NONE: nothing to do).  The launcher below switches on the id; the conditions exist here and nowhere else.
+static int gemm_route(const mfpa_gemm_desc* d, int* id) {
+  *id = MFPA_GEMM_NONE;
   if (!d) return MFPA_EINVAL;
   if (d->batch == 0 || d->M == 0) return MFPA_OK;
   if ((!d->A && !d->c1_x) || !d->W || !d->C || d->batch < 0 || d->M < 0 || d->N < 1 || d->K < GKC || d->K % GKC) return MFPA_EINVAL;
@@ -1745,6 +1748,38 @@ int mfpa_gemm_mfma(const mfpa_gemm_desc* d, void* stream) {
         (d->mode >= 2 && (long long)d->M * d->ldadd + d->npad > lim)) return MFPA_EINVAL;
   }
   if (d->mode == 1 ? (d->N > d->npad / 2) : (d->N > d->npad)) return MFPA_EINVAL;
+  if ((long long)(d->npad / GBN) * ((d->M + GBM - 1) / GBM) * d->batch > 0x3fffffffLL) return MFPA_EINVAL;
+  if (d->precision < 0 || d->precision > 2) return MFPA_EINVAL;
+  if (d->precision == 2 && !(d->K % HKC == 0 && d->K >= 128 && d->npad % WBN == 0 && !d->c1_x)) return MFPA_EINVAL;   // pre-split W: the wide kernel only
+  // K >= 128: the chunked bf16x3 kernel.  (At first the K = 128 / 192 levels ran faster on the fp32 kernel; that was the
+  // epilogue's serialised addend loads and 64-bit addressing, not the arithmetic: with those fixed the fp32 MFMA rate is what
+  // bounds them -- PMC: 2.2 of 4.0 ms MFMA-busy on the K = 192 transposed convolution -- and bf16x3 is 10 % faster end to end.)
+  // 128-column tiles whenever the padded N allows them (precision 2 always does, see above)
+  const bool wide_ok = d->precision >= 1 && d->K % HKC == 0 && d->K >= 128 && d->npad % WBN == 0;
+  if (wide_ok && d->K % (2 * HKC) == 0 && d->M >= PIPE_MIN_M) *id = d->precision == 2 ? MFPA_GEMM_PIPE_WSPLIT : MFPA_GEMM_PIPE;
+  else if (wide_ok) *id = d->precision == 2 ? MFPA_GEMM_WIDE_WSPLIT : MFPA_GEMM_WIDE;
+  else if (d->precision == 1 && d->K % HKC == 0 && d->K >= 128) *id = MFPA_GEMM_BF16X3;
+  else if (d->precision == 1 && d->K == 48 && d->c1_x) *id = MFPA_GEMM_SHORTK48_C1;
+  else if (d->precision == 1 && d->K == 48) *id = MFPA_GEMM_SHORTK48;
+  else if (d->precision == 1 && d->K == 96 && !d->c1_x) *id = MFPA_GEMM_SHORTK96;
+  else if (d->K == 48 && d->c1_x) *id = MFPA_GEMM_SMALLK48_C1;
+  else if (d->K == 48) *id = MFPA_GEMM_SMALLK48;
+  else if (d->c1_x) *id = MFPA_GEMM_MFMA_C1;
+  else *id = MFPA_GEMM_MFMA;
+  return MFPA_OK;
+}
+
+int mfpa_gemm_mfma_route(const mfpa_gemm_desc* d, int* kernel_id) {
+  int id;
+  const int rc = gemm_route(d, &id);
+  if (kernel_id) *kernel_id = id;
+  return rc;
+}
+
+int mfpa_gemm_mfma(const mfpa_gemm_desc* d, void* stream) {
+  int id;
+  const int rc = gemm_route(d, &id);
+  if (rc != MFPA_OK || id == MFPA_GEMM_NONE) return rc;
   GemmArgs a{};
   a.A = d->A; a.lda = d->lda; a.strideA = d->strideA; a.W = d->W; a.bias = d->bias;
   a.addend = d->addend; a.ldadd = d->ldadd; a.strideAdd = d->strideAdd;
@@ -1752,47 +1787,55 @@ int mfpa_gemm_mfma(const mfpa_gemm_desc* d, void* stream) {
   a.C2 = d->C2; a.ldc2 = d->ldc2; a.strideC2 = d->strideC2;
   a.M = d->M; a.N = d->N; a.K = d->K; a.mode = d->mode; a.relu = d->relu;
   a.c1_x = d->c1_x; a.c1_lin = d->c1_lin; a.c1_w = d->c1_w; a.c1_b = d->c1_b;
-  a.ny = (d->M + GBM - 1) / GBM; a.nz = d->batch; a.nx = d->npad / GBN;
-  if ((long long)a.nx * a.ny * a.nz > 0x3fffffffLL) return MFPA_EINVAL;
+  a.ny = (d->M + GBM - 1) / GBM; a.nz = d->batch;
   auto grid1d = [&](int nx) { a.nx = nx; return dim3((unsigned)((((long long)nx * a.ny * a.nz + 7) / 8) * 8)); };
-  dim3 grid = grid1d(d->npad / GBN);
-  if (d->precision < 0 || d->precision > 2) return MFPA_EINVAL;
-  if (d->precision == 2 && !(d->K % HKC == 0 && d->K >= 128 && d->npad % WBN == 0 && !d->c1_x)) return MFPA_EINVAL;   // pre-split W: the wide kernel only
-  // K >= 128: the chunked bf16x3 kernel.  (At first the K = 128 / 192 levels ran faster on the fp32 kernel; that was the
-  // epilogue's serialised addend loads and 64-bit addressing, not the arithmetic: with those fixed the fp32 MFMA rate is what
-  // bounds them -- PMC: 2.2 of 4.0 ms MFMA-busy on the K = 192 transposed convolution -- and bf16x3 is 10 % faster end to end.)
   hipStream_t st = mfpa_stream(stream);
-  // 128-column tiles whenever the padded N allows them (precision 2 always does, see above)
-  const bool wide_ok = d->precision >= 1 && d->K % HKC == 0 && d->K >= 128 && d->npad % WBN == 0;
-  if (wide_ok && d->K % (2 * HKC) == 0 && d->M >= PIPE_MIN_M) {
-    a.ny = (d->M + PBM - 1) / PBM;
-    dim3 gw = grid1d(d->npad / WBN);
-    const unsigned cus8 = (unsigned)((mfpa_current_device_cus() + 7) / 8 * 8);
-    if (cus8 >= 8 && gw.x > cus8) gw.x = cus8;    // persistent: one workgroup per CU walks the tiles (a multiple of 8: XCD ranges)
-    const size_t lds = (size_t)2 * (PBM + WBN) * HROW;
-    if (d->precision == 2) hipLaunchKernelGGL(gemm_bf16x3_pipe_kernel<true>, gw, dim3(512), lds, st, a);
-    else hipLaunchKernelGGL(gemm_bf16x3_pipe_kernel<false>, gw, dim3(512), lds, st, a);
-  } else if (wide_ok) {
-    dim3 gw = grid1d(d->npad / WBN);
-    const size_t lds = (size_t)2 * (GBM + WBN) * HROW;
-    if (d->precision == 2) hipLaunchKernelGGL(gemm_bf16x3_wide_kernel<true>, gw, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL(gemm_bf16x3_wide_kernel<false>, gw, dim3(256), lds, st, a);
-  } else if (d->precision == 1 && d->K % HKC == 0 && d->K >= 128) {
-    hipLaunchKernelGGL(gemm_bf16x3_kernel, grid, dim3(256), 0, mfpa_stream(stream), a);
-  } else if (d->precision == 1 && d->K == 48 && d->c1_x) {
-    hipLaunchKernelGGL((gemm_shortk_bf16x3_kernel<true, 48, 48>), grid, dim3(256), SK_LDS(48) + 9 * 48 * 4, st, a);
-  } else if (d->precision == 1 && d->K == 48) {
-    hipLaunchKernelGGL((gemm_shortk_bf16x3_kernel<false, 48, 48>), grid, dim3(256), SK_LDS(48), st, a);
-  } else if (d->precision == 1 && d->K == 96 && !d->c1_x) {
-    hipLaunchKernelGGL((gemm_shortk_bf16x3_kernel<false, 96, 48>), grid, dim3(256), SK_LDS(48), st, a);
-  } else if (d->K == 48 && d->c1_x) {
-    hipLaunchKernelGGL((gemm_smallk_kernel<true, 48>), grid, dim3(256), 0, mfpa_stream(stream), a);
-  } else if (d->K == 48) {
-    hipLaunchKernelGGL((gemm_smallk_kernel<false, 48>), grid, dim3(256), 0, mfpa_stream(stream), a);
-  } else if (d->c1_x) {
-    hipLaunchKernelGGL(gemm_mfma_kernel<true>, grid, dim3(256), 0, mfpa_stream(stream), a);
-  } else {
-    hipLaunchKernelGGL(gemm_mfma_kernel<false>, grid, dim3(256), 0, mfpa_stream(stream), a);
+  switch (id) {
+    case MFPA_GEMM_PIPE:
+    case MFPA_GEMM_PIPE_WSPLIT: {
+      a.ny = (d->M + PBM - 1) / PBM;
+      dim3 gw = grid1d(d->npad / WBN);
+      const unsigned cus8 = (unsigned)((mfpa_current_device_cus() + 7) / 8 * 8);
+      if (cus8 >= 8 && gw.x > cus8) gw.x = cus8;    // persistent: one workgroup per CU walks the tiles (a multiple of 8: XCD ranges)
+      const size_t lds = (size_t)2 * (PBM + WBN) * HROW;
+      if (id == MFPA_GEMM_PIPE_WSPLIT) hipLaunchKernelGGL(gemm_bf16x3_pipe_kernel<true>, gw, dim3(512), lds, st, a);
+      else hipLaunchKernelGGL(gemm_bf16x3_pipe_kernel<false>, gw, dim3(512), lds, st, a);
+      break;
+    }
+    case MFPA_GEMM_WIDE:
+    case MFPA_GEMM_WIDE_WSPLIT: {
+      dim3 gw = grid1d(d->npad / WBN);
+      const size_t lds = (size_t)2 * (GBM + WBN) * HROW;
+      if (id == MFPA_GEMM_WIDE_WSPLIT) hipLaunchKernelGGL(gemm_bf16x3_wide_kernel<true>, gw, dim3(256), lds, st, a);
+      else hipLaunchKernelGGL(gemm_bf16x3_wide_kernel<false>, gw, dim3(256), lds, st, a);
+      break;
+    }
+    case MFPA_GEMM_BF16X3:
+      hipLaunchKernelGGL(gemm_bf16x3_kernel, grid1d(d->npad / GBN), dim3(256), 0, st, a);
+      break;
+    case MFPA_GEMM_SHORTK48_C1:
+      hipLaunchKernelGGL((gemm_shortk_bf16x3_kernel<true, 48, 48>), grid1d(d->npad / GBN), dim3(256), SK_LDS(48) + 9 * 48 * 4, st, a);
+      break;
+    case MFPA_GEMM_SHORTK48:
+      hipLaunchKernelGGL((gemm_shortk_bf16x3_kernel<false, 48, 48>), grid1d(d->npad / GBN), dim3(256), SK_LDS(48), st, a);
+      break;
+    case MFPA_GEMM_SHORTK96:
+      hipLaunchKernelGGL((gemm_shortk_bf16x3_kernel<false, 96, 48>), grid1d(d->npad / GBN), dim3(256), SK_LDS(48), st, a);
+      break;
+    case MFPA_GEMM_SMALLK48_C1:
+      hipLaunchKernelGGL((gemm_smallk_kernel<true, 48>), grid1d(d->npad / GBN), dim3(256), 0, st, a);
+      break;
+    case MFPA_GEMM_SMALLK48:
+      hipLaunchKernelGGL((gemm_smallk_kernel<false, 48>), grid1d(d->npad / GBN), dim3(256), 0, st, a);
+      break;
+    case MFPA_GEMM_MFMA_C1:
+      hipLaunchKernelGGL(gemm_mfma_kernel<true>, grid1d(d->npad / GBN), dim3(256), 0, st, a);
+      break;
+    case MFPA_GEMM_MFMA:
+      hipLaunchKernelGGL(gemm_mfma_kernel<false>, grid1d(d->npad / GBN), dim3(256), 0, st, a);
+      break;
+    default:
+      return MFPA_EINVAL;
   }
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;

@@ -131,6 +131,43 @@ def test_argument_errors_do_not_touch_the_gpu(lib):
     assert h.mfpa_gemm_mfma(ctypes.byref(m), None) == lib.EINVAL                          # mode 3 needs the addend (the ReLU output)
 
 
+def test_gemm_route_is_host_only_and_rejects_what_the_launcher_rejects(lib):
+    """mfpa_gemm_mfma_route: MFPA_EINVAL exactly where mfpa_gemm_mfma returns it (both go through one host function), no launch, the
+    kernel id for an accepted descriptor, id -1 for the two no-ops."""
+    h = lib.lib()
+    k = ctypes.c_int(7)
+    assert h.mfpa_gemm_mfma_route(None, ctypes.byref(k)) == lib.EINVAL and k.value == -1
+    ok = dict(A=1, lda=128, strideA=0, W=1, C=1, ldc=128, strideC=0, batch=2, M=200, N=100, K=128, npad=128, precision=1)
+    bad = [dict(lda=6), dict(strideA=2), dict(K=24), dict(K=8), dict(W=0), dict(C=0), dict(A=0), dict(batch=-1), dict(M=-1), dict(N=0),
+           dict(N=129), dict(npad=96), dict(npad=0), dict(mode=4), dict(mode=-1), dict(mode=2), dict(mode=3), dict(mode=1, N=65),
+           dict(precision=3), dict(precision=-1), dict(precision=2, K=144), dict(precision=2, npad=192, N=100), dict(precision=2, K=64),
+           dict(ldc=1 << 29), dict(C2=1, ldc2=1 << 29), dict(mode=2, addend=1, ldadd=1 << 29), dict(batch=1 << 24, M=1 << 14, ldc=128),
+           dict(c1_x=1), dict(c1_x=1, c1_w=1, c1_b=1, c1_lin=4 * 199 + 4), dict(c1_x=1, c1_w=1, c1_b=1, c1_lin=4 * 199 + 10),
+           dict(c1_x=1, c1_w=1, c1_b=1, c1_lin=4 * 199 + 8), dict(c1_x=1, c1_w=1, c1_b=1, c1_lin=4 * 199 + 8, precision=2),
+           dict(c1_x=1, c1_w=1, c1_b=1, c1_lin=4 * 199 + 8, precision=0, K=272)]
+    for change in bad:
+        d = lib.GemmDesc(**{**ok, **change})
+        k.value = 7
+        assert h.mfpa_gemm_mfma_route(ctypes.byref(d), ctypes.byref(k)) == lib.EINVAL, change
+        assert k.value == -1, change
+        assert h.mfpa_gemm_mfma(ctypes.byref(d), None) == lib.EINVAL, change               # rejected before any launch (no GPU here)
+    d = lib.GemmDesc(**ok)
+    assert h.mfpa_gemm_mfma_route(ctypes.byref(d), ctypes.byref(k)) == 0 and k.value == 0   # MFPA_GEMM_PIPE
+    assert h.mfpa_gemm_mfma_route(ctypes.byref(d), None) == 0                                # the id is optional
+    d = lib.GemmDesc(**{**ok, "c1_x": 1, "c1_w": 1, "c1_b": 1, "c1_lin": 4 * 199 + 8, "precision": 0, "A": 0})
+    assert h.mfpa_gemm_mfma_route(ctypes.byref(d), ctypes.byref(k)) == 0 and k.value == 10  # MFPA_GEMM_MFMA_C1
+    for change in (dict(batch=0), dict(M=0), dict(batch=0, K=24), dict(M=0, W=0)):           # no-ops come before every other check
+        d = lib.GemmDesc(**{**ok, **change})
+        k.value = 7
+        assert h.mfpa_gemm_mfma_route(ctypes.byref(d), ctypes.byref(k)) == 0 and k.value == -1, change
+        assert h.mfpa_gemm_mfma(ctypes.byref(d), None) == 0, change
+    header = open(os.path.join(ROOT, "include", "mfpa.h")).read()
+    ids = dict((n, int(v)) for n, v in re.findall(r"^\s*(MFPA_GEMM_\w+) = (-?\d+)", header, flags=re.M))
+    assert sorted(ids.values()) == list(range(-1, 12)) and ids["MFPA_GEMM_NONE"] == -1
+    from tests import _gemm_oracle as go
+    assert {n[len("MFPA_GEMM_"):].lower(): v for n, v in ids.items() if v >= 0} == {v: k_ for k_, v in go.KERNEL_NAMES.items()}
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_no_cpu_fallback():
     from musicfpaugment_amd import ops

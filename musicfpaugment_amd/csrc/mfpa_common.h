@@ -44,6 +44,17 @@ __device__ __forceinline__ mfpa_f32x2 mfpa_bcast2(float x) {
   return mfpa_f32x2{lo.x, lo.x};
 }
 
+// four consecutive channels of an NHWC activation tensor kept as float32 or (z16: the plain-bf16 train step's activations) as bfloat16;
+// e = element index of the first of the four
+typedef float mfpa_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ mfpa_f32x4 mfpa_ld_act4(const float* base, size_t e, int z16) {
+  if (z16) {
+    const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + e);
+    return mfpa_f32x4{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
+  }
+  return *reinterpret_cast<const mfpa_f32x4*>(base + e);
+}
+
 // CU count of the CURRENT device (cached per device id: a process may drive several GPUs).  The persistent LSTM kernels size their
 // grids against it -- one workgroup per CU is the residency they rely on (their LDS / register footprint allows no second one).
 static inline int mfpa_current_device_cus() {

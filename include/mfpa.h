@@ -388,17 +388,48 @@ typedef struct mfpa_conv_desc {
   int bwd_z_is_bf16;
 } mfpa_conv_desc;
 int mfpa_conv_mfma(const mfpa_conv_desc* d, void* stream);
+/* HOST function, no GPU needed: validation and kernel choice of mfpa_conv_mfma as one routing step (host arithmetic on the descriptor
+ * only; no pointer is dereferenced).  Returns MFPA_EINVAL exactly where mfpa_conv_mfma does; otherwise MFPA_OK and, in *out when it is
+ * given, the template instantiation that serves `d` -- family MFPA_CONV_NONE for the no-op B == 0.  mfpa_conv_mfma itself launches from
+ * this route; mfpa_conv_scale_folds / mfpa_conv_c1_layout / mfpa_conv_stats_rows answer from the shape rules it uses.  The persistent kernels' grids are
+ * clamped to the device's CUs at launch: that is not part of the route. */
+enum {
+  MFPA_CONV_NONE = -1,
+  MFPA_CONV_WS64 = 0,          /* conv_ws64_kernel<C1SRC> (csrc/unet_ws.hip): inference, bf16x3, w_layout 2, 8 x 32 patch, 64 channels */
+  MFPA_CONV_WD16 = 1,          /* conv_wd16_kernel<PH, PW, ROWS, WMW, SIDE, PLAIN, IN16, AFF16>: w_layout 2, what WS64 does not serve + the training step */
+  MFPA_CONV_MFMA = 2,          /* conv_mfma_kernel<BN, PH, PW, PH * PW / 64, BN / 64, MODE, PREC, C1SRC>: the row image, modes 0 and 2 */
+  MFPA_CONV_CONVT = 3          /* convT_mfma_kernel<PH, PW, PREC, IO16, PLAIN>: mode 1 */
+};
+typedef struct mfpa_conv_route {
+  int family;                  /* MFPA_CONV_* */
+  int ph, pw;                  /* PH x PW: the patch of output pixels [mode 1: input pixels] of one workgroup tile */
+  int bn;                      /* output channels per workgroup (conv_mfma_kernel's BN; 64 for WS64 / CONVT; 32 * (8 / WMW) for WD16) */
+  int wmw;                     /* WD16: WMW, the wave rows (2: 128-channel tiles, 4: 64-channel tiles); else 0 */
+  int mode;                    /* the descriptor's mode (conv_mfma_kernel's MODE: 0 or 2) */
+  int prec;                    /* precision family PREC: 0 = fp32 MFMA, 1 = the bf16 matrix cores (bf16x3, or plain bf16 where `plain`) */
+  int c1src;                   /* C1SRC (WS64, MFMA): source 0 is the fused first layer */
+  int rows, side, plain, in16, aff16;      /* WD16's ROWS / SIDE / PLAIN / IN16 / AFF16 (plain also CONVT's PLAIN) */
+  int io16;                    /* CONVT's IO16: bfloat16 source and / or output */
+  int stats_rows;              /* rows of stats_part written per tile (WD16 with stats_part: WMW), else 0: mfpa_conv_stats_rows =
+                                * ceil(W / pw) * ceil(H / ph) * B * stats_rows */
+} mfpa_conv_route;
+int mfpa_conv_mfma_route(const mfpa_conv_desc* d, mfpa_conv_route* out);
 /* HOST function: the w_layout (0 or 2) the fastest kernel for a (H, W) convolution of this shape reads. */
 int mfpa_conv_weight_layout(int H, int W, int Cin, int Cout, int mode, int precision);
 /* HOST function (round 5): 1 if the INFERENCE launch of this 3x3 shape (precision 1, w_layout 2, no on-load affine, no training side
  * output) runs on conv_ws64_kernel, whose epilogue is cheapest when the output scale is already IN the weights: pass out_scale = NULL
  * with weights pre-multiplied by the per-output-channel scale (then split / fragment-ordered as usual) and out_shift as before -- the shift
  * becomes the accumulators' start value and the epilogue a bare ReLU.  The same call with out_scale given stays valid everywhere.
+ * Answered from the shape rules the route uses, not from a route: where the clip passes conv_ws64_kernel's byte-offset or tile-count limits
+ * (or the 16-bit coordinates / 32-bit byte offsets of every kernel) it still says 1 although the launch runs on conv_wd16_kernel or is
+ * rejected -- folded weights with out_scale = NULL are valid on every kernel.
  * Reference: the folded eval BatchNorm of DoubleConv, training/unet.py:16-21. */
 int mfpa_conv_scale_folds(int H, int W, int Cin, int Cout);
 /* HOST function (round 5): the w_layout the FUSED FIRST-LAYER launch of mfpa_conv_mfma (c1_x32 / c1_spec64 given, 64 -> 64 channels,
  * precision 1) reads at this image size: 2 = the fragment image (conv_ws64_kernel computes the first layer in its loader waves on the
  * matrix cores, bf16x3 like every other layer), 0 = the row image (conv_mfma_kernel computes it with exact fp32 FMAs in its loader).
+ * Answered from the shape rules the route uses: beyond conv_ws64_kernel's byte-offset limit (H * W * 64 * 4 bytes near 2^32) and for H or W
+ * above 32767 it still says 2 although mfpa_conv_mfma rejects that launch.
  * Reference: DoubleConv of `inc`, training/unet.py:16-21, 86. */
 int mfpa_conv_c1_layout(int H, int W);
 /* Round 6: a decoder level's FIRST convolution with the transposed convolution folded into it -- Up.forward of training/unet.py:58-65,
@@ -429,7 +460,9 @@ int mfpa_upconv_pack(const float* w3, const float* wt, const float* bt, const fl
                      float* wc16, float* bias_tab, void* stream);
 int mfpa_upconv_serves(int H, int W, int Hl, int Wl, int Cs, int Cl, int Cout);
 
-/* HOST function: rows of mfpa_conv_desc.stats_part for this shape (0: its kernel does not write them). */
+/* HOST function: rows of mfpa_conv_desc.stats_part for this shape (0: its kernel does not write them) = tiles x mfpa_conv_route.stats_rows
+ * of the launch.  Answered from the shape rules the route uses: it also gives a row count where mfpa_conv_mfma rejects the launch (Cin % 32 != 0
+ * at a multiple-of-128 Cout; H or W above 32767; a clip beyond 32-bit byte offsets), and MFPA_EINVAL above 2^31 - 1 rows. */
 int mfpa_conv_stats_rows(int B, int H, int W, int Cin, int Cout);
 /* stats_part (rows, 2, C) -> sums[2C] float64 as mfpa_bn_stats_sums produces them; workspace as for mfpa_bn_stats. */
 int mfpa_conv_stats_reduce(const float* part, long long rows, int C, double* sums, double* workspace, void* stream);

@@ -21,7 +21,7 @@ EINVAL = -22
 EHIP = -1000
 F32, F64 = 0, 1
 STFT_TABLE_LEN = 1288
-ABI_VERSION = 44
+ABI_VERSION = 45
 
 
 class MfpaError(RuntimeError):
@@ -79,6 +79,7 @@ _SIGNATURES = {
                        c_void_p], c_int),
     "mfpa_conv1x1_out": ([c_void_p, c_longlong, c_int, c_void_p, c_float, c_void_p, c_void_p], c_int),
     "mfpa_conv_mfma": ([c_void_p, c_void_p], c_int),
+    "mfpa_conv_mfma_route": ([c_void_p, c_void_p], c_int),
     "mfpa_conv_weight_layout": ([c_int, c_int, c_int, c_int, c_int, c_int], c_int),
     "mfpa_conv_scale_folds": ([c_int, c_int, c_int, c_int], c_int),
     "mfpa_conv_c1_layout": ([c_int, c_int], c_int),
@@ -210,6 +211,12 @@ class ConvDesc(ctypes.Structure):
                 ("x0_bf16", c_void_p), ("x1_bf16", c_void_p), ("y_bf16", c_void_p), ("stats_part", c_void_p),
                 ("bwd_z", c_void_p), ("bwd_scale", c_void_p), ("bwd_shift", c_void_p), ("bwd_mean", c_void_p), ("bwd_invstd", c_void_p),
                 ("x0_is_bf16", c_int), ("x0_split", c_int), ("x1_split", c_int), ("y_split", c_int), ("y_pool_split", c_int), ("bwd_z_is_bf16", c_int)]
+
+
+class ConvRoute(ctypes.Structure):
+    """mfpa_conv_route of include/mfpa.h."""
+    _fields_ = [(n, c_int) for n in ("family", "ph", "pw", "bn", "wmw", "mode", "prec", "c1src", "rows", "side", "plain", "in16", "aff16",
+                                     "io16", "stats_rows")]
 
 
 class GemmDesc(ctypes.Structure):

@@ -65,9 +65,10 @@ struct UpArgs {
 __attribute__((visibility("hidden"))) int launch_conv_up(UpArgs& a, hipStream_t s);
 __attribute__((visibility("hidden"))) bool conv_up_serves(int H, int W, int Hl, int Wl, int Cs, int Cl, int Cout);
 
-// csrc/unet_ws.hip: the wave-specialised 64-channel 3x3 convolution (inference, bf16x3).  Returns MFPA_OK / a negative code.
-__attribute__((visibility("hidden"))) int launch_conv_ws64(ConvArgs& a, hipStream_t s);
-// does conv_ws64_kernel serve this ConvArgs (checked by the dispatcher before it routes a launch there)?
+// csrc/unet_ws.hip: the wave-specialised 64-channel 3x3 convolution (inference, bf16x3), for a ConvArgs that conv_ws64_serves.  Returns
+// MFPA_OK / a HIP error code.
+template <bool C1SRC> __attribute__((visibility("hidden"))) int launch_conv_ws64(ConvArgs& a, hipStream_t s);     // <false> and <true> exist
+// does conv_ws64_kernel serve this ConvArgs (host arithmetic; asked by conv_route of csrc/unet.hip before it routes a launch there)?
 __attribute__((visibility("hidden"))) bool conv_ws64_serves(const ConvArgs& a);
 
 }  // namespace mfpa_unet

@@ -16,6 +16,8 @@
 // the halo loader; the folded BatchNorm affine + ReLU run in the epilogue on the accumulators.
 // Global loads of the next tap's weights (and next chunk's halo) are issued before the MFMA
 // block of the current tap and written to LDS after it, so they overlap the matrix work.
+#include <cstring>
+
 #include "mfpa_common.h"
 #include "mfpa_conv_tile.h"
 #include "mfpa_unet_args.h"
@@ -1563,16 +1565,8 @@ __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {
   }
 }
 
-// conv_wd16_kernel's ROWS loop form from this many input channels up: same-call pairs on the UNet's layers, 64 clips: +2 .. +4 % at 512 /
-// 1024 input channels, -1 .. -4 % at 64 .. 256 (its longer pipeline fill costs more than the halved fragment reads return when a tile has
-// only 2 .. 8 chunks)
-constexpr int CONV_WD16_ROWS = 512;
-
-template <int PH, int PW, int WMW = 2>
+template <int PH, int PW, bool ROWS, int WMW, bool SIDE, bool PLAIN = false, bool IN16 = false, bool AFF16 = false>
 int launch_wd16(ConvArgs& a, hipStream_t s) {
-  a.tiles_x = (a.W + PW - 1) / PW;
-  a.tiles_y = (a.H + PH - 1) / PH;
-  if ((long long)a.tiles_x * a.tiles_y * a.B > 0x7fffffffLL) return MFPA_EINVAL;
   constexpr int HP = (PW + 2) * (PH + 2);
   constexpr int A_F4 = (HP * (KC / 4) + 511) / 512;
   constexpr int HPS = A_F4 * 64;
@@ -1582,49 +1576,12 @@ int launch_wd16(ConvArgs& a, hipStream_t s) {
                      (a.w1x1 ? (size_t)2 * 256 * sizeof(float) : 0) +                                                             // + the fused OutConv's partial sums
                      (size_t)(2 * 32 * (8 / WMW) + 64) * sizeof(float);                                                           // + the epilogue's constants
   dim3 grid((unsigned)((long long)a.tiles_x * a.tiles_y * a.B), (unsigned)(a.Cout / (32 * (8 / WMW))));
-  const int cin = a.C0 + a.C1;
-  const bool side = a.x0_bf16 || a.x1_bf16 || a.y_bf16 || a.stats_part;
-  const bool rows = WMW == 2 && cin % 64 == 0 && cin >= CONV_WD16_ROWS;
-  if (WMW == 4 || a.plain || (!side && !rows)) {                       // the kernel's PERSIST: one workgroup per CU (and output-channel tile) walks the tiles
+  if constexpr (WMW == 4 || PLAIN || (!SIDE && !ROWS)) {                      // the kernel's PERSIST: one workgroup per CU (and output-channel tile) walks the tiles
     const int cus = mfpa_current_device_cus();
     const unsigned per = (unsigned)((cus > 0 ? cus : 256) / (int)grid.y);
     if (per >= 1 && grid.x > per) grid.x = per;
   }
-  if (a.in16) {                                                        // bf16 source: the plain-bf16 input-gradient convolutions
-    if (!a.plain || a.x1_bf16 || cin % 64) return MFPA_EINVAL;         // (both sources bfloat16; source 1 IS its own bf16 copy)
-    const bool fwd16 = a.in_scale0 != nullptr || a.x0_bf16 != nullptr || (a.y == nullptr && a.bz == nullptr);   // the training forward's form (AFF16)
-    if constexpr (WMW == 4) {
-      if (fwd16) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 4, true, true, true, true>), grid, dim3(512), lds, s, a);
-      else if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 4, true, true, true>), grid, dim3(512), lds, s, a);
-      else hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 4, false, true, true>), grid, dim3(512), lds, s, a);
-    } else {
-      if (fwd16) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, true, 2, true, true, true, true>), grid, dim3(512), lds, s, a);
-      else if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, true, 2, true, true, true>), grid, dim3(512), lds, s, a);
-      else hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, true, 2, false, true, true>), grid, dim3(512), lds, s, a);
-    }
-    MFPA_CHECK_LAUNCH();
-    return MFPA_OK;
-  }
-  if constexpr (WMW == 4) {
-    if (cin % 64) return MFPA_EINVAL;
-    if (a.plain) {
-      if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 4, true, true>), grid, dim3(512), lds, s, a);
-      else hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 4, false, true>), grid, dim3(512), lds, s, a);
-    } else if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 4, true>), grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 4, false>), grid, dim3(512), lds, s, a);
-  } else if (a.plain) {
-    if (cin % 64 == 0) {
-      if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, true, 2, true, true>), grid, dim3(512), lds, s, a);
-      else hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, true, 2, false, true>), grid, dim3(512), lds, s, a);
-    } else if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 2, true, true>), grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 2, false, true>), grid, dim3(512), lds, s, a);
-  } else if (rows) {
-    if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, true, 2, true>), grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, true, 2, false>), grid, dim3(512), lds, s, a);
-  } else {
-    if (side) hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 2, true>), grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, false, 2, false>), grid, dim3(512), lds, s, a);
-  }
+  hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, ROWS, WMW, SIDE, PLAIN, IN16, AFF16>), grid, dim3(512), lds, s, a);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
 }
@@ -1862,19 +1819,11 @@ __global__ __launch_bounds__(256, 2) void convT_mfma_kernel(ConvArgs a) {
   }
 }
 
-template <int PH, int PW, int PREC>
+template <int PH, int PW, int PREC, bool IO16 = false, bool PLAIN = false>
 int launch_convT(ConvArgs& a, hipStream_t s) {
-  a.tiles_x = (a.W + PW - 1) / PW;
-  a.tiles_y = (a.H + PH - 1) / PH;
-  if ((long long)a.tiles_x * a.tiles_y * a.B > 0x7fffffffLL) return MFPA_EINVAL;
   const size_t lds = sizeof(float) * ((size_t)PH * PW * LDK + 4 * (size_t)64 * LDK);
   dim3 grid((unsigned)((long long)a.tiles_x * a.tiles_y * a.B), (unsigned)(a.Cout / 64));
-  if (a.in16 || a.y == nullptr) {
-    if constexpr (PREC == 1) {
-      if (a.plain) hipLaunchKernelGGL((convT_mfma_kernel<PH, PW, PREC, true, true>), grid, dim3(256), lds, s, a);     // round 6: the plain-bf16 training step
-      else hipLaunchKernelGGL((convT_mfma_kernel<PH, PW, PREC, true>), grid, dim3(256), lds, s, a);
-    } else return MFPA_EINVAL;
-  } else hipLaunchKernelGGL((convT_mfma_kernel<PH, PW, PREC>), grid, dim3(256), lds, s, a);
+  hipLaunchKernelGGL((convT_mfma_kernel<PH, PW, PREC, IO16, PLAIN>), grid, dim3(256), lds, s, a);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
 }
@@ -2038,9 +1987,6 @@ template <int BN, int PH, int PW, int WM, int WN, int MODE, int PREC, bool C1SRC
 int launch_conv(ConvArgs& a, hipStream_t s) {
   constexpr int HALO = (MODE == 0) ? 1 : 0;
   constexpr int HP = (PW + 2 * HALO) * (PH + 2 * HALO);
-  a.tiles_x = (a.W + PW - 1) / PW;
-  a.tiles_y = (a.H + PH - 1) / PH;
-  if ((long long)a.tiles_x * a.tiles_y * a.B > 0x7fffffffLL) return MFPA_EINVAL;
   constexpr bool PIPE = conv_is_pipe(WM, WN, MODE, PREC);           // the kernel's PIPE: two padded halo stages
   constexpr int THREADS = 64 * WM * WN;
   constexpr int HPS = PIPE ? ((HP * (KC / 4) + THREADS - 1) / THREADS) * (THREADS / (KC / 4)) : HP;
@@ -2057,17 +2003,55 @@ constexpr int CONV_BIG_MIN_CIN = 64;
 // conv_ws64_kernel also takes outputs of 128 channels and more with at most this many input channels: per layer, 64 clips: 64 -> 128 @
 // 128 x 125 431 -> 380 us, 128 -> 128 725 -> 704, 128 -> 256 @ 64 x 62 360 -> 345; from 256 input channels on it loses
 constexpr int CONV_WS_ALL = 128;
+// conv_wd16_kernel's ROWS loop form from this many input channels up: same-call pairs on the UNet's layers, 64 clips: +2 .. +4 % at 512 /
+// 1024 input channels, -1 .. -4 % at 64 .. 256 (its longer pipeline fill costs more than the halved fragment reads return when a tile has
+// only 2 .. 8 chunks)
+constexpr int CONV_WD16_ROWS = 512;
 
 // Which bf16x3 weight image does the fastest kernel for this shape read?  2 = the fragment-ordered image of the 16 x 16 x 32
 // weights-direct kernels (conv_ws64_kernel, conv_wd16_kernel: 3x3 convolution, >= 64 input channels, the 8 x 32 patches of the wide
 // levels or the 16 x 16 patches of the 16 x 15 level), 0 = the row image.  The 64-channel outputs take it from 64 input channels on:
 // with its persistent tile loop conv_wd16_kernel<.., WMW = 4> beats the plain loop there (64 -> 64 @ 257 x 251, 64 clips, 1366 -> 1008 us).
+// The primary rule: the caller packs the weights by it, so it is an INPUT of the routing below.
 static int conv_weight_layout(int H, int W, int Cin, int Cout, int mode, int precision) {
   if (mode != 0 || precision != 1 || Cin < CONV_BIG_MIN_CIN) return 0;
   const bool wide = W > 16 && H >= 8;
   if (Cout % 128) return (wide && Cout % 64 == 0 && Cin % 64 == 0) ? 2 : 0;     // 64-channel output tiles
   return (wide || (W <= 16 && H >= 16)) ? 2 : 0;
 }
+
+// the two shape rules of the weights-direct kernels that the host queries share with conv_route
+static bool conv_prefers_ws64(int H, int W, int cin, int cout, bool c1) { return W > 16 && H >= 8 && (c1 || cout % 128 || cin <= CONV_WS_ALL); }
+static void conv_wd16_tile(int W, int Cout, mfpa_conv_route* t) {     // 64-channel output tiles: 4 x 2 waves of 64 px x 32 ch
+  t->wmw = Cout % 128 ? 4 : 2; t->bn = 32 * (8 / t->wmw);
+  t->pw = (t->wmw == 2 && W <= 16) ? 16 : 32; t->ph = 256 / t->pw;
+}
+
+// Every kernel of the family that exists, each with the route that names it -- both made from ONE template argument list, so a route cannot
+// reach another instantiation than the one it spells.
+struct ConvKernel { mfpa_conv_route r; int (*launch)(ConvArgs&, hipStream_t); };
+template <bool C1SRC> constexpr ConvKernel k_ws64() { return {{MFPA_CONV_WS64, 8, 32, 64, 0, 0, 1, C1SRC}, mfpa_unet::launch_conv_ws64<C1SRC>}; }
+template <int PH, int PW, bool ROWS, int WMW, bool SIDE, bool PLAIN = false, bool IN16 = false, bool AFF16 = false> constexpr ConvKernel k_wd16() {
+  return {{MFPA_CONV_WD16, PH, PW, 32 * (8 / WMW), WMW, 0, 1, 0, ROWS, SIDE, PLAIN, IN16, AFF16}, launch_wd16<PH, PW, ROWS, WMW, SIDE, PLAIN, IN16, AFF16>}; }
+template <int BN, int PH, int PW, int MODE, int PREC, bool C1SRC = false> constexpr ConvKernel k_mfma() {
+  return {{MFPA_CONV_MFMA, PH, PW, BN, 0, MODE, PREC, C1SRC}, launch_conv<BN, PH, PW, PH * PW / 64, BN / 64, MODE, PREC, C1SRC>}; }
+template <int PH, int PW, int PREC, bool IO16 = false, bool PLAIN = false> constexpr ConvKernel k_convT() {
+  return {{MFPA_CONV_CONVT, PH, PW, 64, 0, 1, PREC, 0, 0, 0, PLAIN, 0, 0, IO16}, launch_convT<PH, PW, PREC, IO16, PLAIN>}; }
+const ConvKernel CONV_KERNELS[] = {
+    k_ws64<false>(), k_ws64<true>(),     // next: <PH, PW, ROWS, WMW, SIDE, PLAIN, IN16, AFF16>; 128-channel tiles: a bf16 source always on the ROWS loop
+    k_wd16<8, 32, 0, 2, 0>(), k_wd16<8, 32, 0, 2, 1>(), k_wd16<8, 32, 1, 2, 0>(), k_wd16<8, 32, 1, 2, 1>(), k_wd16<8, 32, 0, 2, 0, 1>(), k_wd16<8, 32, 0, 2, 1, 1>(),
+    k_wd16<8, 32, 1, 2, 0, 1>(), k_wd16<8, 32, 1, 2, 1, 1>(), k_wd16<8, 32, 1, 2, 0, 1, 1>(), k_wd16<8, 32, 1, 2, 1, 1, 1>(), k_wd16<8, 32, 1, 2, 1, 1, 1, 1>(),
+    k_wd16<16, 16, 0, 2, 0>(), k_wd16<16, 16, 0, 2, 1>(), k_wd16<16, 16, 1, 2, 0>(), k_wd16<16, 16, 1, 2, 1>(), k_wd16<16, 16, 0, 2, 0, 1>(), k_wd16<16, 16, 0, 2, 1, 1>(),
+    k_wd16<16, 16, 1, 2, 0, 1>(), k_wd16<16, 16, 1, 2, 1, 1>(), k_wd16<16, 16, 1, 2, 0, 1, 1>(), k_wd16<16, 16, 1, 2, 1, 1, 1>(), k_wd16<16, 16, 1, 2, 1, 1, 1, 1>(),
+    k_wd16<8, 32, 0, 4, 0>(), k_wd16<8, 32, 0, 4, 1>(), k_wd16<8, 32, 0, 4, 0, 1>(), k_wd16<8, 32, 0, 4, 1, 1>(),                   // 64-channel tiles: no ROWS loop
+    k_wd16<8, 32, 0, 4, 0, 1, 1>(), k_wd16<8, 32, 0, 4, 1, 1, 1>(), k_wd16<8, 32, 0, 4, 1, 1, 1, 1>(),
+    k_mfma<64, 8, 32, 0, 0>(), k_mfma<128, 8, 32, 0, 0>(), k_mfma<128, 4, 32, 0, 0>(), k_mfma<64, 4, 32, 0, 0>(), k_mfma<128, 8, 16, 0, 0>(), k_mfma<64, 8, 16, 0, 0>(),     // <BN, PH, PW, MODE, PREC, C1SRC>
+    k_mfma<64, 8, 32, 0, 1>(), k_mfma<128, 8, 32, 0, 1>(), k_mfma<128, 4, 32, 0, 1>(), k_mfma<64, 4, 32, 0, 1>(), k_mfma<128, 8, 16, 0, 1>(), k_mfma<64, 8, 16, 0, 1>(),
+    k_mfma<64, 8, 32, 2, 0>(), k_mfma<128, 8, 32, 2, 0>(), k_mfma<128, 4, 32, 2, 0>(), k_mfma<64, 4, 32, 2, 0>(), k_mfma<128, 8, 16, 2, 0>(), k_mfma<64, 8, 16, 2, 0>(),
+    k_mfma<64, 8, 32, 2, 1>(), k_mfma<128, 8, 32, 2, 1>(), k_mfma<128, 4, 32, 2, 1>(), k_mfma<64, 4, 32, 2, 1>(), k_mfma<128, 8, 16, 2, 1>(), k_mfma<64, 8, 16, 2, 1>(),
+    k_mfma<128, 16, 16, 0, 1>(), k_mfma<64, 8, 32, 0, 0, true>(), k_mfma<64, 8, 32, 0, 1, true>(),
+    k_convT<4, 32, 0>(), k_convT<4, 32, 1>(), k_convT<4, 32, 1, true>(), k_convT<4, 32, 1, true, true>(),     // <PH, PW, PREC, IO16, PLAIN>
+    k_convT<8, 16, 0>(), k_convT<8, 16, 1>(), k_convT<8, 16, 1, true>(), k_convT<8, 16, 1, true, true>()};
 
 // Tile choice.  Waves always own 64 pixels x 64 channels.
 //   w_layout 2 (bf16x3 3x3 convolution): conv_ws64_kernel (csrc/unet_ws.hip: 4 compute waves of 128 px x 32 ch + 4 loader waves) for the
@@ -2078,83 +2062,11 @@ static int conv_weight_layout(int H, int W, int Cin, int Cout, int mode, int pre
 //                    one-workgroup-per-CU kernel, else 4 waves on 4x32 patches (two workgroups per CU overlap).
 //   otherwise      : 64-channel tiles, 4 waves stacked along M on 8x32 patches (256 x 64).
 //   W <= 16 (the 16x15 bottleneck): 16x16 patches on 8 waves for the bf16x3 3x3 convolution's 128-channel tiles, else 8x16 patches.
-template <int MODE, int PREC>
-int dispatch_conv_p(ConvArgs& a, hipStream_t s) {
-  static_assert(MODE == 0 || MODE == 2, "the transposed convolution (MODE 1) runs on launch_convT");
-  const bool bn128 = (a.Cout % 128 == 0);
-  if constexpr (MODE == 0 && PREC == 1) {
-    if (a.w_frag) {        // w_layout 2: the 16 x 16 x 32 weights-direct kernels
-      if (conv_weight_layout(a.H, a.W, a.C0 + a.C1, a.Cout, 0, 1) != 2 || (a.w1x1 && bn128)) return MFPA_EINVAL;
-      const bool c1 = a.c1_x32 || a.c1_spec64;
-      if ((c1 || !bn128 || a.C0 + a.C1 <= CONV_WS_ALL) && mfpa_unet::conv_ws64_serves(a)) return mfpa_unet::launch_conv_ws64(a, s);
-      if (c1 || a.x0_split || a.x1_split || a.y_split || a.y_pool_split) return MFPA_EINVAL;   // only conv_ws64_kernel knows these
-      if (!bn128) return launch_wd16<8, 32, 4>(a, s);                   // 64-channel output tiles: 4 x 2 waves of 64 px x 32 ch
-      return a.W > 16 ? launch_wd16<8, 32>(a, s) : launch_wd16<16, 16>(a, s);
-    }
-  }
-  const bool big = a.C0 + a.C1 >= ((PREC == 1 && MODE == 0) ? CONV_BIG_MIN_CIN : 256);
-  if (MODE == 0 && (a.c1_x32 || a.c1_spec64)) {        // checked by the caller: C0 == 64, C1 == 0, Cout == 64, W > 16, H >= 8
-    return launch_conv<64, 8, 32, 4, 1, 0, PREC, true>(a, s);
-  }
-  if (a.W > 16 && a.H >= 8) {
-    if (!bn128) return launch_conv<64, 8, 32, 4, 1, MODE, PREC>(a, s);
-    if (big) return launch_conv<128, 8, 32, 4, 2, MODE, PREC>(a, s);
-    return launch_conv<128, 4, 32, 2, 2, MODE, PREC>(a, s);
-  }
-  if (a.W > 16) {
-    return bn128 ? launch_conv<128, 4, 32, 2, 2, MODE, PREC>(a, s) : launch_conv<64, 4, 32, 2, 1, MODE, PREC>(a, s);
-  }
-  if (bn128 && MODE == 0 && PREC == 1 && a.H >= 16) return launch_conv<128, 16, 16, 4, 2, MODE, PREC>(a, s);
-  return bn128 ? launch_conv<128, 8, 16, 2, 2, MODE, PREC>(a, s) : launch_conv<64, 8, 16, 2, 1, MODE, PREC>(a, s);
-}
-
-template <int MODE>
-int dispatch_conv(ConvArgs& a, hipStream_t s, int precision = 0) {
-  // the halo loader packs pixel coordinates into 16 bits each and addresses one clip's input with 32-bit byte offsets
-  if (a.H > 32767 || a.W > 32767) return MFPA_EINVAL;
-  if ((MODE == 2 ? 4LL : 1LL) * a.H * a.W * a.C0 * 4 > 0xffffffffLL || 1LL * a.H1 * a.W1 * a.C1 * 4 > 0xffffffffLL) return MFPA_EINVAL;
-  if constexpr (MODE == 1) {
-    if (precision) return a.W > 16 ? launch_convT<4, 32, 1>(a, s) : launch_convT<8, 16, 1>(a, s);
-    return a.W > 16 ? launch_convT<4, 32, 0>(a, s) : launch_convT<8, 16, 0>(a, s);
-  } else {
-    return precision ? dispatch_conv_p<MODE, 1>(a, s) : dispatch_conv_p<MODE, 0>(a, s);
-  }
-}
-
-}  // namespace
-
-extern "C" {
-
-int mfpa_conv3x3_bn_relu(const float* x0, int C0, const float* x1, int C1, int H1, int W1, int B, int H, int W,
-                         const float* w, int Cout, const float* scale, const float* shift, int relu, int precision,
-                         float* y, void* stream) {
-  if (B == 0) return MFPA_OK;
-  if (!x0 || !w || !y || B < 0 || H < 1 || W < 1) return MFPA_EINVAL;
-  if (C0 < KC || C0 % KC || C1 < 0 || C1 % KC || Cout < 64 || Cout % 64) return MFPA_EINVAL;
-  if (C1 > 0 && (!x1 || H1 < 1 || W1 < 1 || H1 > H || W1 > W)) return MFPA_EINVAL;
-  if (precision != 0 && precision != 1) return MFPA_EINVAL;
-  ConvArgs a{};
-  a.x0 = x0; a.x1 = C1 ? x1 : nullptr; a.w = w; a.scale = scale; a.shift = shift; a.y = y;
-  a.C0 = C0; a.C1 = C1; a.H1 = C1 ? H1 : 0; a.W1 = C1 ? W1 : 0;
-  a.oy1 = C1 ? (H - H1) / 2 : 0;  // F.pad(x1, [dx//2, dx-dx//2, dy//2, dy-dy//2]), unet.py:59-62
-  a.ox1 = C1 ? (W - W1) / 2 : 0;
-  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.relu = relu; a.yH = H; a.yW = W;
-  return dispatch_conv<0>(a, mfpa_stream(stream), precision);
-}
-
-int mfpa_convT2x2(const float* x, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
-                  int precision, float* y, void* stream) {
-  if (B == 0) return MFPA_OK;
-  if (!x || !w || !y || B < 0 || H < 1 || W < 1) return MFPA_EINVAL;
-  if (Cin < KC || Cin % KC || Cout < 64 || Cout % 64 || (precision != 0 && precision != 1)) return MFPA_EINVAL;
-  if (4LL * H * W * Cout * 4 > 0xffffffffLL || 1LL * H * W * Cin * 4 > 0xffffffffLL) return MFPA_EINVAL;   // 32-bit byte offsets inside one clip
-  ConvArgs a{};
-  a.x0 = x; a.w = w; a.scale = nullptr; a.shift = bias; a.y = y;
-  a.C0 = Cin; a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.relu = 0; a.yH = H; a.yW = W;
-  return dispatch_conv<1>(a, mfpa_stream(stream), precision);
-}
-
-int mfpa_conv_mfma(const mfpa_conv_desc* d, void* stream) {
+// Routing: validation and kernel choice of a launch, host arithmetic only -- MFPA_EINVAL, or MFPA_OK with the kernel arguments in `a` and the
+// route in *r (MFPA_CONV_NONE: nothing to do).  Every condition that rejects a launch is here and nowhere else; the launchers size LDS and
+// the grid.  (out_offsets = false: mfpa_conv3x3_bn_relu, which has never checked the output's byte offsets.)
+static int conv_route(const mfpa_conv_desc* d, ConvArgs& a, mfpa_conv_route* r, const ConvKernel** k, bool out_offsets = true) {
+  *r = mfpa_conv_route{}; r->family = MFPA_CONV_NONE; *k = nullptr;
   if (!d) return MFPA_EINVAL;
   if (d->B == 0) return MFPA_OK;
   if ((!d->x0 && !d->c1_x32 && !d->c1_spec64) || !d->w || (!d->y && !d->w1x1 && !d->y_bf16) || d->B < 0 || d->H < 1 || d->W < 1) return MFPA_EINVAL;
@@ -2162,8 +2074,8 @@ int mfpa_conv_mfma(const mfpa_conv_desc* d, void* stream) {
   if (d->mode < 0 || d->mode > 2) return MFPA_EINVAL;
   if (d->C1 > 0 && (d->mode != 0 || !d->x1 || d->H1 < 1 || d->W1 < 1 || d->H1 > d->H || d->W1 > d->W)) return MFPA_EINVAL;
   if ((d->in_scale0 == nullptr) != (d->in_shift0 == nullptr)) return MFPA_EINVAL;
-  if (4LL * d->H * d->W * d->Cout * 4 > 0xffffffffLL) return MFPA_EINVAL;   // the epilogue addresses one clip's output with 32-bit byte offsets
-  ConvArgs a{};
+  if (out_offsets && 4LL * d->H * d->W * d->Cout * 4 > 0xffffffffLL) return MFPA_EINVAL;   // the epilogue addresses one clip's output with 32-bit byte offsets
+  a = ConvArgs{};
   a.x0 = d->x0; a.in_scale0 = d->in_scale0; a.in_shift0 = d->in_shift0;
   a.x1 = d->C1 ? d->x1 : nullptr; a.w = d->w; a.scale = d->out_scale; a.shift = d->out_shift; a.y = d->y;
   a.C0 = d->C0; a.C1 = d->C1; a.H1 = d->C1 ? d->H1 : 0; a.W1 = d->C1 ? d->W1 : 0;
@@ -2200,6 +2112,7 @@ int mfpa_conv_mfma(const mfpa_conv_desc* d, void* stream) {
     return MFPA_EINVAL;
   if (d->x0_is_bf16 && (d->c1_x32 || d->c1_spec64)) return MFPA_EINVAL;
   a.in16 = d->x0_is_bf16 ? 1 : 0;
+  // the split layout: only conv_ws64_kernel reads / writes it (a launch it does not serve is rejected below)
   a.x0_split = d->x0_split ? 1 : 0; a.x1_split = d->x1_split ? 1 : 0; a.y_split = d->y_split ? 1 : 0; a.y_pool_split = d->y_pool_split ? 1 : 0;
   const bool any_split = a.x0_split || a.x1_split || a.y_split || a.y_pool_split;
   if (any_split && (d->mode != 0 || d->precision != 1 || d->w_layout != 2 || (a.x1_split && d->C1 < 1) || (a.y_split && !d->y) || (a.y_pool_split && !d->y_pool) ||
@@ -2219,28 +2132,109 @@ int mfpa_conv_mfma(const mfpa_conv_desc* d, void* stream) {
   if (d->bwd_z != nullptr && d->x0_is_bf16 && (d->in_scale0 || d->x0_bf16)) return MFPA_EINVAL;   // (the training forward's form of the kernel carries no bwd_z code)
   a.bz16 = (d->bwd_z != nullptr && d->bwd_z_is_bf16) ? 1 : 0;
   a.bz = d->bwd_z; a.bz_scale = d->bwd_scale; a.bz_shift = d->bwd_shift; a.bz_mean = d->bwd_mean; a.bz_invstd = d->bwd_invstd;
-  if (any_split) {                                                       // only conv_ws64_kernel reads / writes the split layout
-    if (!mfpa_unet::conv_ws64_serves(a) || (a.Cout % 128 == 0 && d->C0 + d->C1 > CONV_WS_ALL)) return MFPA_EINVAL;
-  }
-  hipStream_t s = mfpa_stream(stream);
   const int prec = d->precision ? 1 : 0;                                 // kernel family: fp32 MFMA or the bf16 matrix cores
-  if (d->mode == 0) return dispatch_conv<0>(a, s, prec);
-  if (d->mode == 1) return dispatch_conv<1>(a, s, prec);
-  return dispatch_conv<2>(a, s, prec);
+  // the halo loader packs pixel coordinates into 16 bits each and addresses one clip's input with 32-bit byte offsets
+  if (a.H > 32767 || a.W > 32767) return MFPA_EINVAL;
+  if ((d->mode == 2 ? 4LL : 1LL) * a.H * a.W * a.C0 * 4 > 0xffffffffLL || 1LL * a.H1 * a.W1 * a.C1 * 4 > 0xffffffffLL) return MFPA_EINVAL;
+  const int cin = a.C0 + a.C1;
+  const bool bn128 = a.Cout % 128 == 0;
+  const bool c1 = a.c1_x32 || a.c1_spec64;
+  mfpa_conv_route t{}; t.mode = d->mode; t.prec = prec;
+  if (d->mode == 1) {                  // the transposed convolution's forward; bfloat16 I/O (and with it the plain-bf16 form) is a bf16x3 instantiation
+    t.family = MFPA_CONV_CONVT; t.bn = 64;
+    t.ph = a.W > 16 ? 4 : 8; t.pw = a.W > 16 ? 32 : 16;
+    t.io16 = a.in16 || a.y == nullptr;
+    t.plain = t.io16 && a.plain;
+    if (t.io16 && prec != 1) return MFPA_EINVAL;
+  } else if (d->mode == 0 && prec == 1 && a.w_frag) {        // w_layout 2: the 16 x 16 x 32 weights-direct kernels
+    if (conv_weight_layout(a.H, a.W, cin, a.Cout, 0, 1) != 2) return MFPA_EINVAL;
+    t.ph = 8; t.pw = 32;
+    if (conv_prefers_ws64(a.H, a.W, cin, a.Cout, c1) && mfpa_unet::conv_ws64_serves(a)) {
+      t.family = MFPA_CONV_WS64; t.bn = 64; t.c1src = c1;
+    } else {
+      if (c1 || a.x0_split || a.x1_split || a.y_split || a.y_pool_split) return MFPA_EINVAL;   // only conv_ws64_kernel knows these
+      t.family = MFPA_CONV_WD16;
+      conv_wd16_tile(a.W, a.Cout, &t);
+      t.plain = a.plain; t.in16 = a.in16;
+      // ... in the training forward's form (AFF16), which carries the side outputs' code whether or not one is asked for
+      t.aff16 = a.in16 && (a.in_scale0 != nullptr || a.x0_bf16 != nullptr || (a.y == nullptr && a.bz == nullptr));
+      t.side = t.aff16 || a.x0_bf16 || a.x1_bf16 || a.y_bf16 || a.stats_part;
+      t.rows = t.wmw == 2 && cin % 64 == 0 && (a.plain || cin >= CONV_WD16_ROWS);
+      t.stats_rows = a.stats_part ? t.wmw : 0;      // [tile * WMW + wm][2][Cout]
+    }
+  } else {                             // conv_mfma_kernel: the row image
+    t.family = MFPA_CONV_MFMA; t.bn = bn128 ? 128 : 64; t.c1src = c1;      // (c1, checked above: Cout == 64, W > 16, H >= 8 -- the 64 x 8 x 32 tile)
+    const bool big = cin >= ((prec == 1 && d->mode == 0) ? CONV_BIG_MIN_CIN : 256);
+    t.pw = a.W > 16 ? 32 : 16;
+    if (a.W > 16) t.ph = (a.H >= 8 && (!bn128 || big)) ? 8 : 4;
+    else t.ph = (bn128 && d->mode == 0 && prec == 1 && a.H >= 16) ? 16 : 8;
+  }
+  a.tiles_x = (a.W + t.pw - 1) / t.pw; a.tiles_y = (a.H + t.ph - 1) / t.ph;
+  if ((long long)a.tiles_x * a.tiles_y * a.B > 0x7fffffffLL) return MFPA_EINVAL;      // one tile per workgroup (or per step of a persistent one): a 32-bit grid extent
+  *r = t; t.stats_rows = 0;            // (stats_rows names no kernel)
+  for (const ConvKernel& e : CONV_KERNELS)
+    if (!memcmp(&e.r, &t, sizeof t)) { *k = &e; return MFPA_OK; }
+  return MFPA_EHIP - (int)hipErrorInvalidDeviceFunction;     // a route without a kernel (none is made above): an error, never another kernel
 }
 
+static int conv_launch(const mfpa_conv_desc* d, void* stream, bool out_offsets = true) {
+  ConvArgs a;
+  mfpa_conv_route r;
+  const ConvKernel* k;
+  const int rc = conv_route(d, a, &r, &k, out_offsets);
+  return k ? k->launch(a, mfpa_stream(stream)) : rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfpa_conv3x3_bn_relu(const float* x0, int C0, const float* x1, int C1, int H1, int W1, int B, int H, int W,
+                         const float* w, int Cout, const float* scale, const float* shift, int relu, int precision,
+                         float* y, void* stream) {
+  if (B == 0) return MFPA_OK;
+  if (!x0 || !w || !y || B < 0 || H < 1 || W < 1) return MFPA_EINVAL;
+  if (C0 < KC || C0 % KC || C1 < 0 || C1 % KC || Cout < 64 || Cout % 64) return MFPA_EINVAL;
+  if (C1 > 0 && (!x1 || H1 < 1 || W1 < 1 || H1 > H || W1 > W)) return MFPA_EINVAL;
+  if (precision != 0 && precision != 1) return MFPA_EINVAL;
+  mfpa_conv_desc d{};                  // (x1 is zero-padded like F.pad(x1, [dx//2, dx-dx//2, dy//2, dy-dy//2]), unet.py:59-62)
+  d.x0 = x0; d.x1 = x1; d.w = w; d.out_scale = scale; d.out_shift = shift; d.y = y;
+  d.C0 = C0; d.C1 = C1; d.H1 = H1; d.W1 = W1; d.B = B; d.H = H; d.W = W; d.Cout = Cout; d.relu = relu; d.precision = precision;
+  return conv_launch(&d, stream, false);
+}
+
+int mfpa_convT2x2(const float* x, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
+                  int precision, float* y, void* stream) {
+  if (B == 0) return MFPA_OK;
+  if (!x || !w || !y || B < 0 || H < 1 || W < 1) return MFPA_EINVAL;
+  if (Cin < KC || Cin % KC || Cout < 64 || Cout % 64 || (precision != 0 && precision != 1)) return MFPA_EINVAL;
+  if (4LL * H * W * Cout * 4 > 0xffffffffLL || 1LL * H * W * Cin * 4 > 0xffffffffLL) return MFPA_EINVAL;   // 32-bit byte offsets inside one clip
+  mfpa_conv_desc d{};
+  d.x0 = x; d.w = w; d.out_shift = bias; d.y = y;
+  d.C0 = Cin; d.B = B; d.H = H; d.W = W; d.Cout = Cout; d.mode = 1; d.precision = precision;
+  return conv_launch(&d, stream);
+}
+
+int mfpa_conv_mfma_route(const mfpa_conv_desc* d, mfpa_conv_route* out) {
+  ConvArgs a;
+  mfpa_conv_route r;
+  const ConvKernel* k;
+  return conv_route(d, a, out ? out : &r, &k);
+}
+
+int mfpa_conv_mfma(const mfpa_conv_desc* d, void* stream) { return conv_launch(d, stream); }
+
+// The three queries below are asked about a SHAPE and answer from the rules conv_route itself calls, not from a route: beyond the limits a
+// launch must also meet they keep the answers they always gave (include/mfpa.h at each; NOTES.md, "one routing function").
 int mfpa_conv_c1_layout(int H, int W) {
   if (H < 1 || W < 1) return MFPA_EINVAL;
   // the fused first-layer launch (mfpa_conv_desc.c1_*, 64 -> 64) reads the fragment image 2 exactly where conv_ws64_kernel<C1SRC> takes it
-  return (conv_weight_layout(H, W, 64, 64, 0, 1) == 2 && W > 16 && H >= 8) ? 2 : 0;
+  return conv_weight_layout(H, W, 64, 64, 0, 1) == 2 ? 2 : 0;     // (64-channel tiles: the wide levels only)
 }
 
 int mfpa_conv_scale_folds(int H, int W, int Cin, int Cout) {
   if (H < 1 || W < 1 || Cin < 1 || Cout < 1) return MFPA_EINVAL;
-  if (conv_weight_layout(H, W, Cin, Cout, 0, 1) != 2 || Cout % 64 || Cin % KC || W <= 16 || H < 8) return 0;
-  // the dispatcher's own routing (dispatch_conv_p): 64-channel-multiple outputs that are not 128-multiples always, the others up to CONV_WS_ALL input channels
-  if (Cout % 128) return 1;
-  return Cin <= CONV_WS_ALL ? 1 : 0;
+  return (conv_weight_layout(H, W, Cin, Cout, 0, 1) == 2 && Cin % KC == 0 && conv_prefers_ws64(H, W, Cin, Cout, false)) ? 1 : 0;
 }
 
 int mfpa_conv_weight_layout(int H, int W, int Cin, int Cout, int mode, int precision) {
@@ -2251,8 +2245,9 @@ int mfpa_conv_weight_layout(int H, int W, int Cin, int Cout, int mode, int preci
 int mfpa_conv_stats_rows(int B, int H, int W, int Cin, int Cout) {
   if (B < 0 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return MFPA_EINVAL;
   if (conv_weight_layout(H, W, Cin, Cout, 0, 1) != 2) return 0;       // no kernel that writes the partials for this shape
-  const int pw = W > 16 ? 32 : 16, ph = 256 / pw;
-  const long long rows = (long long)((W + pw - 1) / pw) * ((H + ph - 1) / ph) * B * (Cout % 128 == 0 ? 2 : 4);
+  mfpa_conv_route t{};
+  conv_wd16_tile(W, Cout, &t);                                         // one row per tile and wave row
+  const long long rows = (long long)((W + t.pw - 1) / t.pw) * ((H + t.ph - 1) / t.ph) * B * t.wmw;
   return rows > 0x7fffffffLL ? MFPA_EINVAL : (int)rows;
 }
 

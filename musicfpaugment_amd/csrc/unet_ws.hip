@@ -680,23 +680,23 @@ bool conv_ws64_serves(const ConvArgs& a) {
   return a.C0 % KC == 0 && a.C1 % KC == 0 && a.C0 + a.C1 >= 64;
 }
 
+// (the caller has asked conv_ws64_serves: conv_route of csrc/unet.hip)
+template <bool C1SRC>
 int launch_conv_ws64(ConvArgs& a, hipStream_t s) {
-  if (!conv_ws64_serves(a)) return MFPA_EINVAL;
   a.tiles_x = (a.W + PW - 1) / PW;
   a.tiles_y = (a.H + PH - 1) / PH;
   const long long ntiles = (long long)a.tiles_x * a.tiles_y * a.B;
-  if (ntiles > 0x7fffffffLL / 2) return MFPA_EINVAL;
-  const bool c1 = a.c1_x32 != nullptr || a.c1_spec64 != nullptr;
-  const size_t lds = 2 * (size_t)STAGE + (256 + 16) * sizeof(float) + (size_t)OUTBUF + (c1 ? (size_t)C1LDS : 0);
+  const size_t lds = 2 * (size_t)STAGE + (256 + 16) * sizeof(float) + (size_t)OUTBUF + (C1SRC ? (size_t)C1LDS : 0);
   const int cus = mfpa_current_device_cus();
   const unsigned gy = (unsigned)(a.Cout / 64);
   unsigned gx = (unsigned)(cus > 0 ? cus : 256) / gy;
   if (gx < 1) gx = 1;
   if ((long long)gx > ntiles) gx = (unsigned)ntiles;
-  if (c1) hipLaunchKernelGGL((conv_ws64_kernel<true>), dim3(gx, gy), dim3(THREADS), lds, s, a);
-  else hipLaunchKernelGGL((conv_ws64_kernel<false>), dim3(gx, gy), dim3(THREADS), lds, s, a);
+  hipLaunchKernelGGL((conv_ws64_kernel<C1SRC>), dim3(gx, gy), dim3(THREADS), lds, s, a);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
 }
+template int launch_conv_ws64<false>(ConvArgs&, hipStream_t);
+template int launch_conv_ws64<true>(ConvArgs&, hipStream_t);
 
 }  // namespace mfpa_unet

@@ -50,6 +50,18 @@ def test_host_only_entry_points(lib):
     assert h.mfpa_lstm_seq_workgroups(64, 768, 0, ctypes.addressof(n)) == 0 and n.value >= 0
     assert h.mfpa_lstm_bwd_seq_workgroups(64, 768, 0, ctypes.addressof(n)) == 0 and n.value >= 0
     assert h.mfpa_lstm_seq_workgroups(64, 768, 0, None) == lib.EINVAL and h.mfpa_lstm_seq_workgroups(64, 100, 0, ctypes.addressof(n)) == lib.EINVAL
+    # the UNet convolution family's route (tests/test_conv_route.py pins the table): host arithmetic, pointers are never dereferenced
+    r = lib.ConvRoute(family=7)
+    d = lib.ConvDesc(x0=1, w=1, y=1, C0=64, C1=0, B=1, H=128, W=125, Cout=64, mode=0, precision=1, w_layout=2)
+    assert h.mfpa_conv_mfma_route(ctypes.byref(d), ctypes.byref(r)) == 0 and (r.family, r.ph, r.pw, r.bn) == (0, 8, 32, 64)   # MFPA_CONV_WS64
+    assert h.mfpa_conv_mfma_route(ctypes.byref(d), None) == 0                                                                  # the route is optional
+    d.B = 0
+    assert h.mfpa_conv_mfma_route(ctypes.byref(d), ctypes.byref(r)) == 0 and r.family == -1                                    # MFPA_CONV_NONE
+    assert h.mfpa_conv_mfma_route(None, ctypes.byref(r)) == lib.EINVAL
+    header = open(os.path.join(ROOT, "include", "mfpa.h")).read()
+    ids = dict((n_, int(v)) for n_, v in re.findall(r"^\s*(MFPA_CONV_\w+) = (-?\d+)", header, flags=re.M))
+    assert ids == {"MFPA_CONV_NONE": -1, "MFPA_CONV_WS64": 0, "MFPA_CONV_WD16": 1, "MFPA_CONV_MFMA": 2, "MFPA_CONV_CONVT": 3}
+    assert h.mfpa_conv_scale_folds(128, 125, 64, 64) == 1 and h.mfpa_conv_c1_layout(257, 251) == 2 and h.mfpa_conv_stats_rows(2, 16, 15, 512, 1024) == 4
 
 
 def test_argument_errors_do_not_touch_the_gpu(lib):

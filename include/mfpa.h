@@ -739,14 +739,14 @@ int mfpa_convT1d_c1_dev(const float* P, int B, int L, int C, const float* w, con
  * order i,f,g,o; model.py:91-110 via nn.LSTM): c (B,H) in/out, hout rows ldh apart; optional hsum = h + addend (the first
  * decoder skip).  whh_grouped = W_hh (4H,H) with rows regrouped to [H/16][i16|f16|g16|o16][H] so a workgroup owns all
  * four gates of its 16 hidden units; xp (B,4H) in the standard gate order, rows ldxp apart, includes both biases.
- * bf16x3 products, fp32 accumulate.  H multiple of 128. */
+ * bf16x3 products, fp32 accumulate.  H multiple of 128.  The mfpa_lstm_* entry points, forward and backward, are csrc/lstm.hip. */
 int mfpa_lstm_step(const float* hprev, long long ldhp, const float* whh_grouped, const float* xp, long long ldxp, float* c,
                    int B, int H, float* hout, long long ldh, float* hsum, const float* addend, long long ldadd, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Demucs training step (training/train.py:275-312, input_type "audio": loss.backward() through training/model.py:290-326).
  * Input gradients are mfpa_gemm_mfma calls on re-laid-out weights (a Conv1d's input gradient is a ConvTranspose1d of the
- * output gradient and vice versa); the entries below are the rest of the backward pass.  csrc/demucs_train.hip. */
+ * output gradient and vice versa); the entries below are the rest of the backward pass.  csrc/demucs_train.hip (mfpa_lstm_*: csrc/lstm.hip). */
 /* mfpa_lstm_step that also keeps what the backward step needs: the gate activations [sig i | sig f | tanh g | sig o] of this
  * step in gsave (B rows ldgs apart; may alias xp) and c_t in cout; the previous cell state is read from cprev (NULL = 0). */
 int mfpa_lstm_step_train(const float* hprev, long long ldhp, const float* whh_grouped, const float* xp, long long ldxp,
@@ -799,7 +799,7 @@ int mfpa_lstm_layer_range(const float* whh_grouped, float* xp, float* hseq, floa
 int mfpa_lstm_layer_bwd_range(const float* whhT, float* gates, const float* cseq, const float* dhout, float* dcstate, int B, int Tn,
                               int H, int t0, int t1, void* stream);
 
-/* mfpa_lstm_layer_range as ONE persistent launch (lstm_seq_kernel, csrc/demucs.hip): a workgroup keeps the W_hh slice of its 16
+/* mfpa_lstm_layer_range as ONE persistent launch (lstm_seq_kernel, csrc/lstm.hip): a workgroup keeps the W_hh slice of its 16
  * hidden units in registers for all steps, the workgroups of a 64-clip slab exchange h[t] through `work` (already split into
  * bf16 hi / lo) and meet at a device-memory counter after every step.  Same arguments and results as mfpa_lstm_layer_range
  * (model.py:91-110, torch.nn.LSTM's recurrence); `work` = device scratch of the size mfpa_lstm_seq_work_bytes reports, owned by this
@@ -818,7 +818,7 @@ int mfpa_lstm_seq_workgroups(int B, int H, int wg_budget, int* workgroups);   /*
 int mfpa_lstm_layer_seq(const float* whh_grouped, float* xp, float* hseq, float* cseq, float* cstate, int B, int Tn, int H, float* xsum,
                         const float* skip, int train, int t0, int t1, int wg_budget, void* work, void* stream);
 
-/* mfpa_lstm_layer_bwd_range as ONE persistent launch (lstm_bwd_seq_kernel, csrc/demucs_train.hip): the backward recurrence of a layer for
+/* mfpa_lstm_layer_bwd_range as ONE persistent launch (lstm_bwd_seq_kernel, csrc/lstm.hip): the backward recurrence of a layer for
  * steps t1-1 .. t0 (torch.nn.LSTM's backward through time, training/train.py:275-312 via autograd in the reference).  A workgroup keeps
  * the W_hh^T rows of its 16 hidden units in registers (16 x 16 x 32 MFMAs, K = 4H), the workgroups of a 64-clip slab exchange dgates[t]
  * through `work` (already split into bf16 hi / lo) and meet at a device-memory counter after every step.  Same arguments and results as

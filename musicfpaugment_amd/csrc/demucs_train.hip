@@ -5,19 +5,19 @@
 // Activations are time-major (B, L, C) like the forward (csrc/demucs.hip).  Input gradients of every Conv1d /
 // ConvTranspose1d / 1x1 / LSTM projection are again strided-window GEMMs served by mfpa_gemm_mfma (a Conv1d's input
 // gradient is a ConvTranspose1d of the output gradient and vice versa); its epilogue applies the ReLU mask of the layer
-// below (mode 3).  This file holds what that kernel cannot express:
+// below (mode 3).  The LSTM's backward recurrence is csrc/lstm.hip.  This file holds what else that kernel cannot express:
 //   gemm_tn_kernel        weight gradients  dW[m][n] += sum_rows dY[row][m] * Xwin[row][n]  (K = every time step of the batch)
 //   glu_bwd_kernel        GLU backward on the packed [32 values | 32 gates] pre-activation tiles the forward saved
-//   lstm_step_bwd_kernel  one backward time step: dh_rec = dgates[t+1] W_hh, then the cell backward, in one launch
 //   downsample2 adjoint, the two 1-channel convolutions' weight gradients, column sums (bias gradients)
 #include "mfpa_common.h"
+#include "mfpa_conv_tile.h"
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 t_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 t_bf16x4 __attribute__((ext_vector_type(4)));
+using mfpa_tile::bf16x4;
+using mfpa_tile::bf16x8;
+using mfpa_tile::f32x4;
+using mfpa_tile::floatx16;
 
 // ---------------------------------------------------------------------------------- weight-gradient GEMM ("TN")
 // C[m][n] += sum_{b < batch} sum_{r < R} A[b*strideA + r*lda + m] * Bm[b*strideB + r*ldb + n]
@@ -182,11 +182,11 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs a) {
 typedef short t_s16x4 __attribute__((ext_vector_type(4)));
 constexpr int HKC_T = 32;
 
-__device__ __forceinline__ t_bf16x8 tn_tr_frag(const char* p0, const char* p1) {
+__device__ __forceinline__ bf16x8 tn_tr_frag(const char* p0, const char* p1) {
   typedef t_s16x4 __attribute__((address_space(3))) * lds_ptr;
   const t_s16x4 u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(p0));
   const t_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(p1));
-  union { short s[8]; t_bf16x8 b; } r;
+  union { short s[8]; bf16x8 b; } r;
 #pragma unroll
   for (int j = 0; j < 4; ++j) { r.s[j] = u[j]; r.s[4 + j] = v[j]; }
   return r.b;
@@ -241,14 +241,14 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(TnArgs a) {
     }
   };
   auto split_store = [&](char* row, int q, int lo_off, f32x4 v) __attribute__((always_inline)) {
-    t_bf16x4 hi, lo;
+    bf16x4 hi, lo;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       hi[k] = (__bf16)v[k];
       lo[k] = (__bf16)(v[k] - (float)hi[k]);
     }
-    *reinterpret_cast<t_bf16x4*>(row + 8 * q) = hi;
-    if (!PLAIN) *reinterpret_cast<t_bf16x4*>(row + lo_off + 8 * q) = lo;
+    *reinterpret_cast<bf16x4*>(row + 8 * q) = hi;
+    if (!PLAIN) *reinterpret_cast<bf16x4*>(row + lo_off + 8 * q) = lo;
   };
   auto store = [&](int buf) __attribute__((always_inline)) {
 #pragma unroll
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(TnArgs a) {
       const char* Bp = Bs + buf * HKC_T * ROWB + b_off;
 #pragma unroll
       for (int ks = 0; ks < HKC_T / 16; ++ks) {
-        t_bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
+        bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           const char* p = Ap + 16 * ks * ROWA + 64 * i;
@@ -481,413 +481,6 @@ __global__ __launch_bounds__(256) void downsample2_adj_kernel(const float* __res
   }
 }
 
-// ---------------------------------------------------------------------------------- LSTM backward time step
-// One launch per step t (t = T-1 .. 0):
-//   dh    = dhout[t] + dgates[t+1] W_hh                      (GEMM, K = 4H; skipped at t = T-1)
-//   do = dh tanh(c_t) o (1-o);  dc = dc_next + dh o (1 - tanh^2 c_t);  di = dc g i (1-i);  df = dc c_{t-1} f (1-f);
-//   dg = dc i (1-g^2);  dc_next <- dc f;   dgates[t] overwrites the saved gate activations [i | f | g | o] of step t.
-// A workgroup owns 64 clips x 32 hidden units: B operand = rows u of W_hh^T (H, 4H).  8 waves = (clip half) x (K quarter of
-// every 128-wide chunk); bf16x3 products like the forward step; workgroup id -> (XCD, slot) so that an XCD's three unit
-// groups keep their 1.2 MB of W_hh^T in that XCD's L2 for all steps.
-constexpr int BKC = 128;
-constexpr int BROW = 4 * BKC + 16;       // LDS row bytes [128 hi | 128 lo | pad]
-constexpr int BU = 32;
-constexpr int BTHREADS = 512;
-constexpr int BPF = 6;                   // chunks of global loads in flight per thread
-
-// MT: 32-clip tiles per workgroup: 2 = (clip half) x (K quarter), 1 = K eighths (small batches: twice the workgroups).
-// BUT: hidden units per workgroup, 32 or 16 (16: the matrix tile is half empty, but the step is bound by the bytes a workgroup
-// streams -- 32 x 3072 gate gradients + BUT x 3072 weights -- and twice as many CUs pull them).
-template <int MT, int BUT>
-__global__ __launch_bounds__(BTHREADS, 1) void lstm_step_bwd_kernel(const float* __restrict__ dgnext, long long ldgn,
-                                                                    const float* __restrict__ whhT, float* gs, long long ldgs,
-                                                                    const float* __restrict__ ct, long long ldct,
-                                                                    const float* __restrict__ cprev, long long ldcp,
-                                                                    const float* __restrict__ dhout, long long lddh,
-                                                                    float* __restrict__ dcstate, int B, int H, int mtiles) {
-  constexpr int BBM = 32 * MT;               // clips per workgroup
-  constexpr int WK = 8 / MT;                 // k-step groups
-  constexpr int KS = 8 / WK;                 // k-steps of 16 per wave and chunk
-  constexpr int FA = BBM * 32 / BTHREADS;    // float4 per thread per chunk for the dgates rows (2 MT)
-  extern __shared__ __attribute__((aligned(16))) char lsm[];
-  char* As = lsm;                            // [2][BBM][BROW]
-  char* Bs = lsm + 2 * BBM * BROW;           // [2][32][BROW]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int wm = wave % MT, wk = wave / MT;  // wk: k-steps KS wk .. of each chunk
-  const int ngroups = H / BUT;
-  int grp, mt;
-  {
-    const int id = blockIdx.x, total = ngroups * mtiles;
-    const int per_xcd = (total + 7) / 8;
-    const int lin = (id % 8) * per_xcd + id / 8;
-    if (lin >= total) return;                // uniform per workgroup, before any barrier
-    grp = lin / mtiles; mt = lin % mtiles;
-  }
-  const int m0 = mt * BBM;
-  const int K = 4 * H;
-  floatx16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-  if (dgnext != nullptr) {
-    const float* Wg = whhT + (size_t)grp * BUT * K;
-    const int nk = K / BKC;
-    constexpr int FB = BUT / 16;                       // float4 per thread per chunk for the weight rows
-    if (BUT < 32) {                                    // rows BUT .. 31 of both weight buffers are never staged: keep them zero
-      for (int i = tid; i < 2 * (32 - BUT) * (BROW / 16); i += BTHREADS) {
-        const int buf = i / ((32 - BUT) * (BROW / 16)), rem = i % ((32 - BUT) * (BROW / 16));
-        *reinterpret_cast<f32x4*>(Bs + (buf * 32 + BUT + rem / (BROW / 16)) * BROW + 16 * (rem % (BROW / 16))) = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-    // register ring of BPF chunks of global loads (the step is latency-bound: dgates[t+1] was written by the previous launch)
-    f32x4 ar[BPF][FA], br[BPF][FB];
-    const int q = tid & 31, r0 = tid >> 5;             // column quad, first row; rows r0 + 16 i
-    auto load = [&](int kc, f32x4 (&a4)[FA], f32x4 (&b2)[FB]) __attribute__((always_inline)) {
-#pragma unroll
-      for (int i = 0; i < FA; ++i) {
-        const int m = m0 + r0 + 16 * i;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (m < B) v = *reinterpret_cast<const f32x4*>(dgnext + (size_t)m * ldgn + kc * BKC + 4 * q);
-        a4[i] = v;
-      }
-#pragma unroll
-      for (int i = 0; i < FB; ++i) b2[i] = *reinterpret_cast<const f32x4*>(Wg + (size_t)(r0 + 16 * i) * K + kc * BKC + 4 * q);
-    };
-    auto split_store = [&](char* row, f32x4 v) __attribute__((always_inline)) {
-      t_bf16x4 hi, lo;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        hi[k] = (__bf16)v[k];
-        lo[k] = (__bf16)(v[k] - (float)hi[k]);
-      }
-      *reinterpret_cast<t_bf16x4*>(row + 8 * q) = hi;
-      *reinterpret_cast<t_bf16x4*>(row + 2 * BKC + 8 * q) = lo;
-    };
-    auto store = [&](int buf, f32x4 (&a4)[FA], f32x4 (&b2)[FB]) __attribute__((always_inline)) {
-#pragma unroll
-      for (int i = 0; i < FA; ++i) split_store(As + (buf * BBM + r0 + 16 * i) * BROW, a4[i]);
-#pragma unroll
-      for (int i = 0; i < FB; ++i) split_store(Bs + (buf * 32 + r0 + 16 * i) * BROW, b2[i]);
-    };
-#pragma unroll
-    for (int j = 0; j < BPF; ++j)
-      if (j < nk) load(j, ar[j], br[j]);
-    for (int base = 0; base < nk; base += BPF) {
-#pragma unroll
-      for (int j = 0; j < BPF; ++j) {
-        const int kc = base + j;
-        if (kc < nk) {                                   // uniform over the workgroup
-          const int buf = kc & 1;
-          store(buf, ar[j], br[j]);                      // buffer (kc & 1) was last read for chunk kc - 2, before the previous barrier
-          if (kc + BPF < nk) load(kc + BPF, ar[j], br[j]);
-          __syncthreads();
-          const char* Ap = As + (buf * BBM + wm * 32 + li) * BROW + 16 * lh;
-          const char* Bp = Bs + (buf * 32 + li) * BROW + 16 * lh;
-#pragma unroll
-          for (int s = KS * wk; s < KS * wk + KS; ++s) {
-            const t_bf16x8 ah = *reinterpret_cast<const t_bf16x8*>(Ap + 32 * s);
-            const t_bf16x8 al = *reinterpret_cast<const t_bf16x8*>(Ap + 2 * BKC + 32 * s);
-            const t_bf16x8 bh = *reinterpret_cast<const t_bf16x8*>(Bp + 32 * s);
-            const t_bf16x8 bl = *reinterpret_cast<const t_bf16x8*>(Bp + 2 * BKC + 32 * s);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-          }
-        }
-      }
-    }
-    __syncthreads();                                     // the slabs below reuse the operand buffers
-  }
-  // the WK partial tiles -> LDS slabs [WK][BBM clips][36], summed by the cell threads
-  float* G = reinterpret_cast<float*>(lsm);
-  constexpr int GLDW = 36;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int m = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-    G[(wk * BBM + m) * GLDW + li] = acc[r];
-  }
-  __syncthreads();
-  constexpr int UQ = BUT / 4;                  // unit quads per clip
-  const int clip = tid / UQ, uq = tid % UQ;
-  const int m = m0 + clip;
-  if (clip < BBM && m < B) {
-    const int u0 = grp * BUT + 4 * uq;
-    f32x4 dh = *reinterpret_cast<const f32x4*>(dhout + (size_t)m * lddh + u0);
-#pragma unroll
-    for (int w = 0; w < WK; ++w) dh += *reinterpret_cast<const f32x4*>(G + (w * BBM + clip) * GLDW + 4 * uq);
-    float* gr = gs + (size_t)m * ldgs;
-    const f32x4 vi = *reinterpret_cast<const f32x4*>(gr + u0), vf = *reinterpret_cast<const f32x4*>(gr + H + u0);
-    const f32x4 vg = *reinterpret_cast<const f32x4*>(gr + 2 * H + u0), vo = *reinterpret_cast<const f32x4*>(gr + 3 * H + u0);
-    const f32x4 c = *reinterpret_cast<const f32x4*>(ct + (size_t)m * ldct + u0);
-    const f32x4 cp = cprev ? *reinterpret_cast<const f32x4*>(cprev + (size_t)m * ldcp + u0) : f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 dcs = *reinterpret_cast<const f32x4*>(dcstate + (size_t)m * H + u0);
-    f32x4 di, df, dg, dO;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float tc = tanhf(c[k]);
-      dO[k] = dh[k] * tc * vo[k] * (1.f - vo[k]);
-      const float dc = dcs[k] + dh[k] * vo[k] * (1.f - tc * tc);
-      di[k] = dc * vg[k] * vi[k] * (1.f - vi[k]);
-      df[k] = dc * cp[k] * vf[k] * (1.f - vf[k]);
-      dg[k] = dc * vi[k] * (1.f - vg[k] * vg[k]);
-      dcs[k] = dc * vf[k];
-    }
-    *reinterpret_cast<f32x4*>(gr + u0) = di;
-    *reinterpret_cast<f32x4*>(gr + H + u0) = df;
-    *reinterpret_cast<f32x4*>(gr + 2 * H + u0) = dg;
-    *reinterpret_cast<f32x4*>(gr + 3 * H + u0) = dO;
-    *reinterpret_cast<f32x4*>(dcstate + (size_t)m * H + u0) = dcs;
-  }
-}
-
-
-// ---------------------------------------------------------------------------------- persistent LSTM backward layer
-// The backward recurrence of a layer for steps t1-1 .. t0 in ONE launch: lstm_seq_kernel's scheme (demucs.hip) turned round.
-//   dh[t] = dhout[t] + dgates[t+1] W_hh  is K = 4H long and 16 hidden units wide per workgroup, so the weights only fit the
-//   registers with the 16 x 16 x 32 MFMA: wave w of 8 holds the B-fragments of W_hh^T rows u0 .. u0+15, K range [w 4H/8, ..):
-//   KS = H / 64 k-steps x (hi, lo) x 4 VGPRs (96 at H = 768), read once per launch instead of once per step;
-//   dgates[t+1] (64 clips x 4H, already split [32 hi | 32 lo] by the cells that produced it) is exchanged through a ping-pong
-//   buffer with agent-scope stores / buffer loads, A-fragments read straight from it; the 8 partial 64 x 16 tiles meet in LDS;
-//   a cell thread owns (clip, 2 units): dc lives in its registers, the saved gate activations / cell states / dhout of step t are
-//   fetched before the wait; it writes dgates[t] over the activations (the weight-gradient GEMMs read them later) and into the
-//   exchange buffer.  Slab counter, bounded waits and the error word as in lstm_seq_kernel.
-constexpr int QB_W = 8;
-constexpr int QB_GLD = 17;
-constexpr unsigned QB_SPIN_LIMIT = 1u << 22;
-constexpr int QB_SYNC_WORDS = 1024, QB_ERR_WORD = 512;
-
-struct LstmBwdSeqArgs {
-  const float* whhT;      // (H, 4H)
-  float* gates;           // (B, Tn, 4H): activations [i | f | g | o] in, pre-activation gradients out
-  const float* cseq;      // (B, Tn, H)
-  const float* dhout;     // (B, Tn, H)
-  float* dcstate;         // (B, H): read when t1 < Tn, written at the end
-  unsigned* sync;
-  char* gsplit;           // [2][B][4H * 4 bytes]
-  int B, Tn, H, t0, t1, nslab, ngroups;
-};
-
-// MTB = 16-clip MFMA row tiles per workgroup (slab = 16 MTB clips).  A workgroup reads its slab's WHOLE dgates[t+1] row block every
-// step (K = 4H: 12 KB per clip), four times the forward's bytes, and a CU pulls ~60 GB/s of such loads: small batches therefore use
-// small slabs, so that more CUs share the reading (64 clips: 192 workgroups of 16 clips instead of 48 of 64).
-template <int KS, int MTB>          // k-steps of 32 per wave: 4H = 256 KS
-__global__ __launch_bounds__(64 * QB_W, 1) void lstm_bwd_seq_kernel(LstmBwdSeqArgs a) {
-  constexpr int SLAB = 16 * MTB;
-  constexpr int UPT = MTB == 4 ? 2 : 1;                     // hidden units per cell thread
-  constexpr int TPC = 16 / UPT;                             // cell threads per clip
-  __shared__ __attribute__((aligned(16))) float G[QB_W * SLAB * QB_GLD];
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ln = lane & 15, kg = lane >> 4;
-  const int H = a.H, K = 4 * a.H;
-  int slab, grp;
-  {
-    const int id = blockIdx.x, total = a.nslab * a.ngroups;
-    const int per_xcd = (total + 7) / 8;
-    const int lin = (id % 8) * per_xcd + id / 8;
-    if (lin >= total) return;                               // padding workgroups are not counted at the barrier
-    slab = lin / a.ngroups; grp = lin % a.ngroups;
-  }
-  const int m0 = slab * SLAB, u0 = grp * 16;
-  unsigned* cnt = a.sync + 16 * slab;
-  unsigned* err = a.sync + QB_ERR_WORD;
-  const unsigned members = (unsigned)a.ngroups;
-  const size_t rowb = (size_t)K * 4, bufb = (size_t)a.B * rowb;
-
-  // ---- W_hh^T fragments of this workgroup's 16 units, split once
-  t_bf16x8 wh[KS], wl[KS];
-  {
-    const float* Wr = a.whhT + (size_t)(u0 + ln) * K + (size_t)wave * KS * 32 + 8 * kg;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(Wr + 32 * s), v1 = *reinterpret_cast<const f32x4*>(Wr + 32 * s + 4);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const __bf16 h0 = (__bf16)v0[k], h1 = (__bf16)v1[k];
-        wh[s][k] = h0; wh[s][4 + k] = h1;
-        wl[s][k] = (__bf16)(v0[k] - (float)h0); wl[s][4 + k] = (__bf16)(v1[k] - (float)h1);
-      }
-    }
-  }
-  // ---- cell threads: clip tid / TPC, hidden units u .. u + UPT - 1
-  const int clip = tid / TPC, ui = tid % TPC;
-  const int m = m0 + clip;
-  const bool live = clip < SLAB && m < a.B;
-  const int u = u0 + UPT * ui;
-  const size_t ldg = (size_t)a.Tn * K, ldh = (size_t)a.Tn * H;
-  auto put_split = [&](char* buf, int q, const float (&v)[UPT]) __attribute__((always_inline)) {   // gate q of this thread's units -> the exchange rows
-    const int col = q * H + u;
-    char* p = buf + (size_t)(live ? m : 0) * rowb + (size_t)(col >> 5) * 128 + (size_t)(col & 31) * 2;
-    if (UPT == 2) {
-      const __bf16 h0 = (__bf16)v[0], h1 = (__bf16)v[UPT - 1];
-      const __bf16 l0 = (__bf16)(v[0] - (float)h0), l1 = (__bf16)(v[UPT - 1] - (float)h1);
-      const unsigned hi = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
-      const unsigned lo = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
-      __hip_atomic_store(reinterpret_cast<unsigned*>(p), hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(reinterpret_cast<unsigned*>(p + 64), lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      const __bf16 h0 = (__bf16)v[0];
-      const __bf16 l0 = (__bf16)(v[0] - (float)h0);
-      __hip_atomic_store(reinterpret_cast<unsigned short*>(p), __builtin_bit_cast(unsigned short, h0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(reinterpret_cast<unsigned short*>(p + 64), __builtin_bit_cast(unsigned short, l0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  };
-  float dc[UPT];
-#pragma unroll
-  for (int k = 0; k < UPT; ++k) dc[k] = 0.f;
-  if (live) {
-    char* buf = a.gsplit + (size_t)(a.t1 & 1) * bufb;                // dgates[t] live in buffer t & 1
-    if (a.t1 < a.Tn) {                                               // a later range has run: its dgates[t1] and dc
-      const float* gr = a.gates + (size_t)m * ldg + (size_t)a.t1 * K + u;
-#pragma unroll
-      for (int k = 0; k < UPT; ++k) dc[k] = a.dcstate[(size_t)m * H + u + k];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float v[UPT];
-#pragma unroll
-        for (int k = 0; k < UPT; ++k) v[k] = gr[q * H + k];
-        put_split(buf, q, v);
-      }
-    } else {
-      float z[UPT];
-#pragma unroll
-      for (int k = 0; k < UPT; ++k) z[k] = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) put_split(buf, q, z);
-    }
-  }
-  bool dead = false;
-  auto arrive = [&]() __attribute__((always_inline)) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  auto wait = [&](unsigned round) __attribute__((always_inline)) {
-    if (tid == 0 && !dead) {
-      const unsigned target = round * members;
-      unsigned n = 0;
-      while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-        if ((++n & 63u) == 0u && (n > QB_SPIN_LIMIT || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-          __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          dead = true;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-    __syncthreads();
-  };
-  arrive();
-
-  unsigned arow[MTB];
-#pragma unroll
-  for (int mt = 0; mt < MTB; ++mt) {
-    int r = m0 + mt * 16 + ln;
-    r = r < a.B ? r : a.B - 1;
-    arow[mt] = (unsigned)((size_t)r * rowb + (size_t)wave * KS * 128 + 16 * kg);          // k-step s = chunk wave KS + s of the row
-  }
-  const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(a.gsplit, 0, (int)(2 * bufb), 0x00020000);
-  constexpr int PF = (MTB == 4) ? 2 : (KS < 4 ? KS : 4);    // k-steps of A loads in flight (8 MTB VGPRs each)
-  for (int t = a.t1 - 1; t >= a.t0; --t) {
-    // what the cell needs of step t does not depend on the recurrence: fetch it before the wait
-    float gv[4][UPT], ct[UPT], cp[UPT], dho[UPT];
-#pragma unroll
-    for (int k = 0; k < UPT; ++k) { gv[0][k] = gv[1][k] = gv[2][k] = gv[3][k] = 0.f; ct[k] = cp[k] = dho[k] = 0.f; }
-    if (live) {
-      const float* gr = a.gates + (size_t)m * ldg + (size_t)t * K + u;
-      const size_t o = (size_t)m * ldh + (size_t)t * H + u;
-#pragma unroll
-      for (int k = 0; k < UPT; ++k) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gv[q][k] = gr[q * H + k];
-        ct[k] = a.cseq[o + k];
-        if (t > 0) cp[k] = a.cseq[o + k - H];
-        dho[k] = a.dhout[o + k];
-      }
-    }
-    wait((unsigned)(a.t1 - t));
-    const unsigned pb = (unsigned)(((t + 1) & 1) * bufb);
-    f32x4 acc[MTB];
-#pragma unroll
-    for (int mt = 0; mt < MTB; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    t_bf16x8 fa[PF][MTB][2];
-    auto issue = [&](int s, t_bf16x8 (&f)[MTB][2]) __attribute__((always_inline)) {
-#pragma unroll
-      for (int mt = 0; mt < MTB; ++mt) {
-        const unsigned o = pb + arow[mt] + (unsigned)s * 128u;
-        f[mt][0] = __builtin_bit_cast(t_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(grsrc, o, 0, 16));
-        f[mt][1] = __builtin_bit_cast(t_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(grsrc, o + 64, 0, 16));
-      }
-    };
-#pragma unroll
-    for (int s = 0; s < PF; ++s) issue(s, fa[s]);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-#pragma unroll
-      for (int mt = 0; mt < MTB; ++mt) {
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s % PF][mt][1], wh[s], acc[mt], 0, 0, 0);
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s % PF][mt][0], wl[s], acc[mt], 0, 0, 0);
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s % PF][mt][0], wh[s], acc[mt], 0, 0, 0);
-      }
-      if (s + PF < KS) issue(s + PF, fa[s % PF]);
-    }
-    // partial tiles -> LDS: D[row = 4 kg + j][col = ln] of m-tile mt
-#pragma unroll
-    for (int mt = 0; mt < MTB; ++mt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) G[(wave * SLAB + mt * 16 + 4 * kg + j) * QB_GLD + ln] = acc[mt][j];
-    __syncthreads();
-    if (live) {
-      float dg_[4][UPT];
-#pragma unroll
-      for (int k = 0; k < UPT; ++k) {
-        float dh = dho[k];
-#pragma unroll
-        for (int w = 0; w < QB_W; ++w) dh += G[(w * SLAB + clip) * QB_GLD + UPT * ui + k];
-        const float vi = gv[0][k], vf = gv[1][k], vg = gv[2][k], vo = gv[3][k];
-        const float tc = tanhf(ct[k]);
-        dg_[3][k] = dh * tc * vo * (1.f - vo);
-        const float dcv = dc[k] + dh * vo * (1.f - tc * tc);
-        dg_[0][k] = dcv * vg * vi * (1.f - vi);
-        dg_[1][k] = dcv * cp[k] * vf * (1.f - vf);
-        dg_[2][k] = dcv * vi * (1.f - vg * vg);
-        dc[k] = dcv * vf;
-      }
-      char* buf = a.gsplit + (size_t)(t & 1) * bufb;
-      float* gr = a.gates + (size_t)m * ldg + (size_t)t * K + u;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        put_split(buf, q, dg_[q]);
-#pragma unroll
-        for (int k = 0; k < UPT; ++k) gr[q * H + k] = dg_[q][k];
-      }
-    }
-    if (t > a.t0) arrive();                                  // (its __syncthreads also frees the partial-tile slabs)
-  }
-  if (live) {
-#pragma unroll
-    for (int k = 0; k < UPT; ++k) a.dcstate[(size_t)m * H + u + k] = dc[k];
-  }
-}
-
-static int lstm_bwd_seq_cus() { return mfpa_current_device_cus(); }
-
-// slab size (mtb x 16 clips) and resident workgroups of the persistent backward launch; 0 = the per-step path
-static int lstm_bwd_seq_plan(int B, int H, int wg_budget, int* mtb_out) {
-  const int ks = (H % 64 == 0) ? H / 64 : 0, ngroups = H / 16;
-  const int cus = lstm_bwd_seq_cus();
-  const int budget = (wg_budget > 0 && wg_budget < cus) ? wg_budget : cus;
-  int mtb = 0;
-  for (int c = 1; c <= 4 && !mtb; c *= 2)
-    if ((long long)((B + 16 * c - 1) / (16 * c)) * ngroups <= budget) mtb = c;
-  const int nslab = mtb ? (B + 16 * mtb - 1) / (16 * mtb) : 0;
-  if (mtb_out) *mtb_out = mtb;
-  if (!mtb || !(ks == 4 || ks == 8 || ks == 12) || nslab > 32 || (long long)B * H * 32 > 0x7fffffffLL || (long long)nslab * ngroups > budget)
-    return 0;
-  return nslab * ngroups;
-}
-
 }  // namespace
 
 extern "C" {
@@ -977,100 +570,6 @@ int mfpa_downsample2_adjoint(const float* dy, int B, int ldy, int nout, const fl
   if (!dy || !kernel112 || !dx || B < 0 || B > 65535 || T < 2 || nout < 1 || nout > (T + 1) / 2 || ldy < nout) return MFPA_EINVAL;
   int gx = (T + 255) / 256; if (gx > 1024) gx = 1024;
   hipLaunchKernelGGL(downsample2_adj_kernel, dim3(gx, B), dim3(256), 0, mfpa_stream(stream), dy, ldy, nout, kernel112, scale, T, dx);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
-}
-
-int mfpa_lstm_step_bwd(const float* dgnext, long long ldgn, const float* whhT, float* gates, long long ldg, const float* ct,
-                       long long ldct, const float* cprev, long long ldcp, const float* dhout, long long lddh, float* dcstate, int B,
-                       int H, void* stream) {
-  if (B == 0) return MFPA_OK;
-  if (!whhT || !gates || !ct || !dhout || !dcstate || B < 0 || H < BKC || H % BKC) return MFPA_EINVAL;
-  if (ldgn % 4 || ldg % 4 || ldct % 4 || ldcp % 4 || lddh % 4) return MFPA_EINVAL;
-  const int MT = ((long long)(H / BU) * ((B + 31) / 32) <= 256) ? 1 : 2;   // 32-clip tiles while they leave the chip under-filled
-  const int but = (MT == 1 && (long long)(H / 16) * ((B + 31) / 32) <= 128) ? 16 : 32;   // 16-unit groups while even those leave half the chip free
-  const int mtiles = (B + 32 * MT - 1) / (32 * MT);
-  const long long total = (long long)(H / but) * mtiles;
-  if (total > 0x7fffff) return MFPA_EINVAL;
-  const unsigned grid = (unsigned)(((total + 7) / 8) * 8);
-  const size_t lds = (size_t)2 * (32 * MT + 32) * BROW;
-  if (MT == 1 && but == 16)
-    hipLaunchKernelGGL((lstm_step_bwd_kernel<1, 16>), dim3(grid), dim3(BTHREADS), lds, mfpa_stream(stream), dgnext, ldgn, whhT, gates, ldg,
-                       ct, ldct, cprev, ldcp, dhout, lddh, dcstate, B, H, mtiles);
-  else if (MT == 1)
-    hipLaunchKernelGGL((lstm_step_bwd_kernel<1, 32>), dim3(grid), dim3(BTHREADS), lds, mfpa_stream(stream), dgnext, ldgn, whhT, gates, ldg,
-                       ct, ldct, cprev, ldcp, dhout, lddh, dcstate, B, H, mtiles);
-  else
-    hipLaunchKernelGGL((lstm_step_bwd_kernel<2, 32>), dim3(grid), dim3(BTHREADS), lds, mfpa_stream(stream), dgnext, ldgn, whhT, gates, ldg,
-                       ct, ldct, cprev, ldcp, dhout, lddh, dcstate, B, H, mtiles);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
-}
-
-/* The backward recurrence of a whole LSTM layer: mfpa_lstm_step_bwd for t = Tn-1 .. 0 from one host loop.  gates / cseq / dhout
- * are (B, Tn, .) as mfpa_lstm_layer_range(train = 1) left them; dcstate (B, H) scratch (zeroed here). */
-int mfpa_lstm_layer_bwd_range(const float* whhT, float* gates, const float* cseq, const float* dhout, float* dcstate, int B, int Tn,
-                              int H, int t0, int t1, void* stream) {
-  if (B == 0 || Tn == 0 || t1 <= t0) return MFPA_OK;
-  if (!whhT || !gates || !cseq || !dhout || !dcstate || B < 0 || Tn < 0 || t0 < 0 || t1 > Tn) return MFPA_EINVAL;
-  if (t1 == Tn) MFPA_HIP(hipMemsetAsync(dcstate, 0, (size_t)B * H * sizeof(float), mfpa_stream(stream)));
-  const long long ldg = (long long)Tn * 4 * H, ldh = (long long)Tn * H;
-  for (int t = t1 - 1; t >= t0; --t) {
-    const int rc = mfpa_lstm_step_bwd(t + 1 < Tn ? gates + (size_t)(t + 1) * 4 * H : nullptr, ldg, whhT, gates + (size_t)t * 4 * H, ldg,
-                                      cseq + (size_t)t * H, ldh, t ? cseq + (size_t)(t - 1) * H : nullptr, ldh, dhout + (size_t)t * H, ldh,
-                                      dcstate, B, H, stream);
-    if (rc != MFPA_OK) return rc;
-  }
-  return MFPA_OK;
-}
-
-/* mfpa_lstm_layer_bwd_range as ONE persistent launch (lstm_bwd_seq_kernel): same arguments and results; `work` = device scratch of the
- * size mfpa_lstm_bwd_seq_work_bytes reports, owned by this layer while the call runs, zeroed once before its first use; the error
- * word (bounded waits, as for mfpa_lstm_layer_seq) sits at the same byte offset.  Shapes outside the persistent kernel's range
- * (H / 64 not in {4, 8, 12}, more workgroups than `wg_budget` even with 64-clip slabs) take the per-step path inside the same call.
- * wg_budget: how many workgroups this launch may keep resident (0 = one per CU); a caller running two such launches at once passes half. */
-int mfpa_lstm_bwd_seq_work_bytes(int B, int H, long long* bytes) {
-  if (!bytes || B < 0 || H < 0) return MFPA_EINVAL;
-  *bytes = (long long)QB_SYNC_WORDS * 4 + 2LL * B * 4 * H * 4;
-  return MFPA_OK;
-}
-
-int mfpa_lstm_bwd_seq_workgroups(int B, int H, int wg_budget, int* workgroups) {
-  if (!workgroups || B < 0 || H < 64) return MFPA_EINVAL;
-  *workgroups = B > 0 ? lstm_bwd_seq_plan(B, H, wg_budget, nullptr) : 0;
-  return MFPA_OK;
-}
-
-int mfpa_lstm_layer_bwd_seq(const float* whhT, float* gates, const float* cseq, const float* dhout, float* dcstate, int B, int Tn, int H,
-                            int t0, int t1, int wg_budget, void* work, void* stream) {
-  if (B == 0 || Tn == 0 || t1 <= t0) return MFPA_OK;
-  if (!whhT || !gates || !cseq || !dhout || !dcstate || !work || B < 0 || Tn < 0 || t0 < 0 || t1 > Tn || H < 64) return MFPA_EINVAL;
-  const int ks = (H % 64 == 0) ? H / 64 : 0, ngroups = H / 16;
-  // the smallest slab (16, 32 or 64 clips) whose workgroups still fit the chip: more CUs share the reading of dgates[t+1]
-  // (every workgroup of a launch must be resident at once: at most wg_budget of them, 0 = one per CU)
-  int mtb = 0;
-  const int wgs = lstm_bwd_seq_plan(B, H, wg_budget, &mtb);
-  if (wgs == 0)
-    return mfpa_lstm_layer_bwd_range(whhT, gates, cseq, dhout, dcstate, B, Tn, H, t0, t1, stream);
-  const int nslab = (B + 16 * mtb - 1) / (16 * mtb);
-  LstmBwdSeqArgs a;
-  a.whhT = whhT; a.gates = gates; a.cseq = cseq; a.dhout = dhout; a.dcstate = dcstate;
-  a.sync = reinterpret_cast<unsigned*>(work);
-  a.gsplit = reinterpret_cast<char*>(work) + (size_t)QB_SYNC_WORDS * 4;
-  a.B = B; a.Tn = Tn; a.H = H; a.t0 = t0; a.t1 = t1; a.nslab = nslab; a.ngroups = ngroups;
-  hipStream_t st = mfpa_stream(stream);
-  MFPA_HIP(hipMemsetAsync(work, 0, (size_t)QB_ERR_WORD * 4, st));           // the slab counters; the error word stays
-  const unsigned grid = (unsigned)(((nslab * ngroups + 7) / 8) * 8);
-#define QB_LAUNCH(KS_)                                                                                         \
-  if (mtb == 1) hipLaunchKernelGGL((lstm_bwd_seq_kernel<KS_, 1>), dim3(grid), dim3(64 * QB_W), 0, st, a);      \
-  else if (mtb == 2) hipLaunchKernelGGL((lstm_bwd_seq_kernel<KS_, 2>), dim3(grid), dim3(64 * QB_W), 0, st, a); \
-  else hipLaunchKernelGGL((lstm_bwd_seq_kernel<KS_, 4>), dim3(grid), dim3(64 * QB_W), 0, st, a)
-  switch (ks) {
-    case 4: QB_LAUNCH(4); break;
-    case 8: QB_LAUNCH(8); break;
-    default: QB_LAUNCH(12); break;
-  }
-#undef QB_LAUNCH
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
 }

@@ -1,4 +1,4 @@
-"""Demucs forward over the C ABI (csrc/demucs.hip): weight packing and the layer schedule.
+"""Demucs forward over the C ABI (csrc/demucs.hip, the LSTM recurrence csrc/lstm.hip): weight packing and the layer schedule.
 
 Reference: Demucs.forward, training/model.py:290-326.  Activations are (B, L, C) float32 tensors."""
 from __future__ import annotations
@@ -178,22 +178,21 @@ def _lstm_work(dev, layer: int, B: int, H: int, backward: bool = False) -> torch
     """Scratch of the persistent LSTM kernel for one layer (mfpa_lstm_layer_seq): the exchange buffers of h and the slab counters.
     Kept per (device, stream, layer, shape).  Every entry handed out is remembered until lstm_results_ok() has looked at its error
     word -- the operators call that before their results leave them (demucs_forward, DemucsTrainEngine.train_step)."""
-    L = lib()
-    size_fn = L.mfpa_lstm_bwd_seq_work_bytes if backward else L.mfpa_lstm_seq_work_bytes      # the backward form exchanges 4H columns
+    def zeros():             # one layout for both directions (csrc/lstm.hip); the backward form exchanges 4H columns
+        nbytes = ctypes.c_longlong(0)
+        size_fn = lib().mfpa_lstm_bwd_seq_work_bytes if backward else lib().mfpa_lstm_seq_work_bytes
+        check(size_fn(B, H, ctypes.addressof(nbytes)), "mfpa_lstm_seq_work_bytes")
+        return torch.zeros(nbytes.value // 4, dtype=torch.int32, device=dev)
+
     if torch.cuda.is_current_stream_capturing():
         # inside a HIP graph capture: scratch from the graph's own pool, zeroed by a captured fill on every replay; no host-side
         # look at the error word (nothing may synchronise or query here) -- a replayed graph reports through its results only
-        nbytes = ctypes.c_longlong(0)
-        check(size_fn(B, H, ctypes.addressof(nbytes)), "mfpa_lstm_seq_work_bytes")
-        return torch.zeros(nbytes.value // 4, dtype=torch.int32, device=dev)
+        return zeros()
     st = torch.cuda.current_stream(dev)
     key = (_dev_index(dev), st.cuda_stream, layer, B, H, backward)
     ent = _LSTM_WORK.get(key)
     if ent is None:
-        nbytes = ctypes.c_longlong(0)
-        check(size_fn(B, H, ctypes.addressof(nbytes)), "mfpa_lstm_seq_work_bytes")
-        buf = torch.zeros(nbytes.value // 4, dtype=torch.int32, device=dev)
-        ent = _LSTM_WORK[key] = [buf, torch.zeros(1, dtype=torch.int32).pin_memory()]
+        ent = _LSTM_WORK[key] = [zeros(), torch.zeros(1, dtype=torch.int32).pin_memory()]
     touched = _LSTM_TOUCHED.setdefault(key[0], [])
     if not any(e is ent for e in touched):
         touched.append(ent)

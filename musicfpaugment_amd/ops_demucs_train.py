@@ -15,7 +15,7 @@ zero gradients, so Adam leaves them at zero):
   step, exactly as encI's input-gradient operand is derived from encI.w.  LSTM W_ih / W_hh as nn.LSTM stores them.
 Weight re-layouts (transposes for the input-gradient GEMMs) are device copies made once per step (19 M parameters).
 
-Input gradients run through mfpa_gemm_mfma (ops_demucs.gemm); weight gradients through mfpa_gemm_tn; see csrc/demucs_train.hip.
+Input gradients run through mfpa_gemm_mfma (ops_demucs.gemm); weight gradients through mfpa_gemm_tn; see csrc/demucs_train.hip (the LSTM backward recurrence: csrc/lstm.hip).
 """
 from __future__ import annotations
 
@@ -443,7 +443,7 @@ class DemucsTrainEngine:
             bwgs = D.lstm_seq_workgroups(B, H, 0, backward=True) if bwork is not None else 0
 
             def bwd(whhT, gates, cseq, dhout, dc):
-                if bwork is not None:            # one persistent launch for the layer (csrc/demucs_train.hip: lstm_bwd_seq_kernel)
+                if bwork is not None:            # one persistent launch for the layer (csrc/lstm.hip: lstm_bwd_seq_kernel)
                     done = D._GUARD.admit(dev, bwgs)
                     check(L.mfpa_lstm_layer_bwd_seq(ptr(whhT), ptr(gates), ptr(cseq), ptr(dhout), ptr(dc), B, Tn, H, 0, Tn, 0,
                                                     ptr(bwork[id(gates)]), stream()), "mfpa_lstm_layer_bwd_seq")

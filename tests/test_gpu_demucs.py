@@ -122,30 +122,13 @@ def test_presplit_weights_give_the_same_bits(net):
     assert torch.equal(y_split, y_fly)
 
 
-def _lstm_reference(x, skip, wih, bias, whh):
-    """torch.nn.LSTM's recurrence (model.py:91-110) in float64 on the CPU: two layers, then + skip."""
-    B, Tn, H = x.shape
-    inp = x.double()
-    for k in range(2):
-        h = torch.zeros(B, H, dtype=torch.float64)
-        c = torch.zeros(B, H, dtype=torch.float64)
-        out = []
-        for t in range(Tn):
-            g = inp[:, t] @ wih[k].double().t() + bias[k].double() + h @ whh[k].double().t()
-            i, f, gg, o = g.split(H, dim=1)
-            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-            h = torch.sigmoid(o) * torch.tanh(c)
-            out.append(h)
-        inp = torch.stack(out, dim=1)
-    return inp + skip.double()
-
-
 @pytest.mark.parametrize("B,Tn,H,train", [(70, 9, 256, False), (256, 7, 768, False), (33, 6, 768, True), (130, 20, 512, False), (65, 5, 1024, True)])
 def test_persistent_lstm_layer(B, Tn, H, train):
     """mfpa_lstm_layer_seq (one persistent launch per layer: W_hh in registers, h exchanged in split form, slab barriers in
     device memory) against the float64 recurrence and against the per-step kernels; ragged slabs, both chunked (two streams) and
     whole-sequence forms, the training form's saved gates and cell states; no wait may have given up."""
     from musicfpaugment_amd import ops_demucs as D
+    from tests._lstm_reference import lstm_reference
     g = torch.Generator().manual_seed(B + Tn)
     x = torch.randn(B, Tn, H, generator=g) * 0.5
     skip = torch.randn(B, Tn, H, generator=g)
@@ -153,7 +136,7 @@ def test_persistent_lstm_layer(B, Tn, H, train):
     whh = [torch.randn(4 * H, H, generator=g) / np.sqrt(H) for _ in range(2)]
     bias = [torch.randn(4 * H, generator=g) * 0.1 for _ in range(2)]
     grouped = [w.reshape(4, H // 16, 16, H).permute(1, 0, 2, 3).reshape(4 * H, H).contiguous().cuda() for w in whh]
-    want = _lstm_reference(x, skip, wih, bias, whh)
+    want = lstm_reference(x, skip, wih, bias, whh)
     dev = lambda ts: [t.cuda() for t in ts]
     runs = {}
     old = (D.PERSISTENT_LSTM, D.LSTM_CHUNK)

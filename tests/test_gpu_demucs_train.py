@@ -397,6 +397,7 @@ def test_persistent_lstm_backward_layer(B, Tn, H):
     (the chunked pipeline's use), ragged slabs; and against the float64 recurrence of the same backward."""
     from musicfpaugment_amd._lib import check, lib, ptr, stream
     from musicfpaugment_amd import ops_demucs as D
+    from tests._lstm_reference import lstm_layer_backward
     L = lib()
     g = torch.Generator().manual_seed(B * Tn)
     gates0 = torch.cat([torch.rand(B, Tn, H, generator=g), torch.rand(B, Tn, H, generator=g), torch.rand(B, Tn, H, generator=g) * 2 - 1,
@@ -405,25 +406,7 @@ def test_persistent_lstm_backward_layer(B, Tn, H):
     dhout = (torch.randn(B, Tn, H, generator=g) * 0.1).contiguous()
     whh = torch.randn(4 * H, H, generator=g) / np.sqrt(H)
     whhT = whh.t().contiguous()                                                                # (H, 4H)
-    # float64 recurrence
-    W = whh.double()
-    dgn = torch.zeros(B, 4 * H, dtype=torch.float64)
-    dc = torch.zeros(B, H, dtype=torch.float64)
-    want = torch.zeros(B, Tn, 4 * H, dtype=torch.float64)
-    for t in range(Tn - 1, -1, -1):
-        vi, vf, vg, vo = [x.double() for x in gates0[:, t].split(H, dim=1)]
-        ct = cseq[:, t].double()
-        cp = cseq[:, t - 1].double() if t else torch.zeros_like(ct)
-        dh = dhout[:, t].double() + dgn @ W
-        tc = torch.tanh(ct)
-        dO = dh * tc * vo * (1 - vo)
-        dcv = dc + dh * vo * (1 - tc * tc)
-        di = dcv * vg * vi * (1 - vi)
-        df = dcv * cp * vf * (1 - vf)
-        dg = dcv * vi * (1 - vg * vg)
-        dc = dcv * vf
-        dgn = torch.cat([di, df, dg, dO], dim=1)
-        want[:, t] = dgn
+    want, dc = lstm_layer_backward(gates0, cseq, dhout, whh)                                  # the float64 recurrence
     dev = lambda t: t.clone().cuda()
     whhT_d, cseq_d, dhout_d = dev(whhT), dev(cseq), dev(dhout)
     outs = {}

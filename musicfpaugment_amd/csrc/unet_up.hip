@@ -20,6 +20,9 @@
 // 16 consecutive 16-byte pieces of a plane) and then the low-resolution half: per 32-channel chunk a 6 x 18 patch of `low` and four
 // (ty, tx) "pairs" -- the two column phases of a pair are the two halves of what a tap is in the skip half, each half with its own
 // weight fragments (the wave's row phase and the half's column phase pick the composite), a ring of two pairs of register sets.
+// A fragment set the wave already holds is not read again: the column-odd half of a tap and the column-even half of the next tap in the row
+// read the same bytes (likewise the halves of a pair row), so a tap row costs four sets of reads for its six half-steps and a pair row three
+// for four (see the compute waves' comments); the MFMA order, and with it every output bit, is that of one read per half-step.
 #include "mfpa_common.h"
 #include "mfpa_conv_tile.h"
 #include "mfpa_unet_args.h"
@@ -269,31 +272,35 @@ __global__ __launch_bounds__(THREADS, 1) void conv_up_kernel(UpArgs a) {
     load_w_at(rs_up, (t16 * (unsigned)nup + (unsigned)chunk) * wrow + wcol, SLOT);
   };
   struct XFrags { frag_t h[4], l[4]; };                                 // PREC 0: h = piece 2 g, l = piece 2 g + 1
-  XFrags fx0, fx1;
+  XFrags fx[2];
   // fragment of group (j, px) -- tile rows 2 j + wm, columns 2 p + px:
   //   skip, tap (ta, tb): halo row 2 j + wm + ta, halo column 2 p + s with s = px + tb -> staged position (s & 1) * 17 + (s >> 1) + p
-  //   low, pair (ty, tx): patch row j + ty + wm, patch column p + tx + px
+  //   low, pair (ty, tx): patch row j + ty + wm, patch column p + c with c = tx + px
+  // Only s (c) of (px, tb) ((px, tx)) enters the address, so a tap row's six half-steps read FOUR distinct fragment sets s = 0 .. 3 (feeding
+  // 1, 2, 2, 1 consecutive half-steps) and a pair row's four half-steps THREE, c = 0 .. 2 (1, 2, 1): each set is read once.  Set d of a chunk
+  // (skip: 4 ta + s, low: 3 ty + c) lives in fx[d & 1]; a chunk has an even number of sets, so every chunk starts in fx[0].  The next set's
+  // eight reads go under the half-steps that use the current one: all under a sole user, groups 0, 1 / 2, 3 under a first / second user.
   // PREC 1: plane (hi, g) and, HLS further, (lo, g); PREC 0: pieces 2 g and 2 g + 1 = planes (g >> 1, 2 (g & 1)) and the next one
   const int pl0 = PREC == 1 ? plane_off(0, g) : plane_off(g >> 1, 2 * (g & 1));
   constexpr int SECOND = PREC == 1 ? HLS : PLANE;                      // (planes 2 k and 2 k + 1 are PLANE apart: plane_off)
   const int xb_skip = (wm * HPW + p) * 16 + pl0;
   const int xb_up = (wm * LPW + p) * 16 + pl0;
-  auto read_at = [&](XFrags& f, const char* base, auto STRIDE) __attribute__((always_inline)) {
-    constexpr int stride = decltype(STRIDE)::value;
+  constexpr int R_ALL = 0, R_FIRST = 1, R_SECOND = 2;                  // which groups of a set one half-step reads: 0 .. 3, 0 .. 1, 2 .. 3
+  auto read_at = [&](XFrags& f, const char* base, auto STRIDE, auto PART) __attribute__((always_inline)) {
+    constexpr int stride = decltype(STRIDE)::value, part = decltype(PART)::value;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = (part == R_SECOND ? 2 : 0); j < (part == R_FIRST ? 2 : 4); ++j) {
       const char* r = base + j * stride;
       f.l[j] = *reinterpret_cast<const frag_t*>(r + SECOND);
       f.h[j] = *reinterpret_cast<const frag_t*>(r);
     }
   };
-  auto read_skip = [&](XFrags& f, const char* stage, auto TAP, auto PX) __attribute__((always_inline)) {
-    constexpr int tap = decltype(TAP)::value, s = decltype(PX)::value + tap % 3;
-    read_at(f, stage + xb_skip + ((tap / 3) * HPW + (s & 1) * HALF + (s >> 1)) * 16, std::integral_constant<int, 2 * HPW * 16>{});
+  auto read_skip = [&](XFrags& f, const char* stage, auto TA, auto S, auto PART) __attribute__((always_inline)) {
+    constexpr int ta = decltype(TA)::value, s = decltype(S)::value;
+    read_at(f, stage + xb_skip + (ta * HPW + (s & 1) * HALF + (s >> 1)) * 16, std::integral_constant<int, 2 * HPW * 16>{}, PART);
   };
-  auto read_up = [&](XFrags& f, const char* stage, auto PAIR, auto PX) __attribute__((always_inline)) {
-    constexpr int pair = decltype(PAIR)::value;
-    read_at(f, stage + xb_up + ((pair >> 1) * LPW + (pair & 1) + decltype(PX)::value) * 16, std::integral_constant<int, LPW * 16>{});
+  auto read_up = [&](XFrags& f, const char* stage, auto TY, auto C, auto PART) __attribute__((always_inline)) {
+    read_at(f, stage + xb_up + (decltype(TY)::value * LPW + decltype(C)::value) * 16, std::integral_constant<int, LPW * 16>{}, PART);
   };
   floatx4 acc[2][PT];
 #pragma unroll
@@ -332,76 +339,97 @@ __global__ __launch_bounds__(THREADS, 1) void conv_up_kernel(UpArgs a) {
       for (int i = 0; i < 4; ++i) acc[ct][4 * half + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[ct][0], f.h[i], acc[ct][4 * half + i], 0, 0, 0);
     }
   };
-  constexpr int N_R = 8, N_M = PREC == 1 ? 24 : 64, N_W = 4;                            // fragment reads / MFMAs of one half, weight loads of one set
+  constexpr int N_M = PREC == 1 ? 24 : 64, N_W = 4;                    // MFMAs of one half, weight loads of one set
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
-  auto pin_half_with_loads = [&]() __attribute__((always_inline)) {   // MFMAs interleaved with the half's 8 fragment reads, then its 4 weight loads
-    pin_reads<N_M - 1, N_R>();
-    constexpr int used = pin_read_slots(N_M - 1, N_R);
+  using I2 = std::integral_constant<int, 2>;
+  using RAll = std::integral_constant<int, R_ALL>;
+  using RFirst = std::integral_constant<int, R_FIRST>;
+  using RSecond = std::integral_constant<int, R_SECOND>;
+  // PART of the next set read under this half -> its fragment reads (16 bytes each): 8 or 4
+  auto pin_half_with_loads = [&](auto PART) __attribute__((always_inline)) {   // MFMAs interleaved with the half's fragment reads, then its 4 weight loads
+    constexpr int n_r = decltype(PART)::value == R_ALL ? 8 : 4;
+    pin_reads<N_M - 1, n_r>();
+    constexpr int used = pin_read_slots(N_M - 1, n_r);
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
     __builtin_amdgcn_sched_group_barrier(0x020, N_W, 0);
     if constexpr (N_M - used - 1 > 0) __builtin_amdgcn_sched_group_barrier(0x008, N_M - used - 1, 0);
     __builtin_amdgcn_sched_barrier(0);
   };
-  auto pin_half = [&]() __attribute__((always_inline)) {
-    pin_reads<N_M, N_R>();
-    if constexpr (N_M - pin_read_slots(N_M, N_R) > 0) __builtin_amdgcn_sched_group_barrier(0x008, N_M - pin_read_slots(N_M, N_R), 0);
+  auto pin_half = [&](auto PART) __attribute__((always_inline)) {
+    constexpr int n_r = decltype(PART)::value == R_ALL ? 8 : 4;
+    pin_reads<N_M, n_r>();
+    if constexpr (N_M - pin_read_slots(N_M, n_r) > 0) __builtin_amdgcn_sched_group_barrier(0x008, N_M - pin_read_slots(N_M, n_r), 0);
     __builtin_amdgcn_sched_barrier(0);
   };
   int kpar = 0;                                                        // parity of the stage the current chunk is read from
 
-  // One skip tap.  Half A: MFMA(column-even groups) || read the column-odd groups' fragments, request the weights two taps ahead.  Half B:
-  // MFMA(column-odd groups) || read the column-even fragments of the next tap.  The chunk's barrier sits between the halves of tap 8.
+  // One skip tap (ta, tb), b = tb & 1.  Half A (column-even groups, set s = tb in fx[b]): MFMA || read set s + 1 into fx[b ^ 1] -- all of it
+  // when tb = 0 (set 0 has this one user), else groups 2, 3 (half B of the previous tap read groups 0, 1) -- and request the weights two taps
+  // ahead.  Half B (column-odd groups, set s = tb + 1 in fx[b ^ 1]): MFMA || read groups 0, 1 of set s + 1 into fx[b], or, when tb = 2 (set 3
+  // has this one user), all of the next tap row's set 0.  The chunk's barrier sits between the halves of tap 8.
   // NEXT_UP (tap 7 / 8 only): the next chunk is the first low-resolution chunk (its pair 0 goes into sets 0 / 1), else a skip chunk.
   auto skip_tap = [&](auto TAP, int chunk, auto FIRST, auto NEXT_UP) __attribute__((always_inline)) {
-    constexpr int tap = decltype(TAP)::value;
+    constexpr int tap = decltype(TAP)::value, ta = tap / 3, tb = tap % 3, b = tb & 1;
     constexpr bool next_up = decltype(NEXT_UP)::value;
+    using TA = std::integral_constant<int, ta>;
+    using PART_A = std::conditional_t<tb == 0, RAll, RSecond>;
+    using PART_B = std::conditional_t<tb == 2, RAll, RFirst>;
     const char* cur = smem + kpar * STAGE;
-    read_skip(fx1, cur, TAP, I1{});
-    mfma_half(fx0, wq[tap % 3], I0{}, FIRST);
+    read_skip(fx[b ^ 1], cur, TA{}, std::integral_constant<int, tb + 1>{}, PART_A{});
+    mfma_half(fx[b], wq[tap % 3], I0{}, FIRST);
     if constexpr (tap + 2 < 9) load_w_skip(chunk, tap + 2, std::integral_constant<int, (tap + 2) % 3>{});
     else if constexpr (next_up) load_w_up(0, 0, tap - 7, std::integral_constant<int, tap - 7>{});
     else load_w_skip(chunk + 1, tap - 7, std::integral_constant<int, tap - 7>{});
-    pin_half_with_loads();
+    pin_half_with_loads(PART_A{});
     if constexpr (tap == 8) {
       __syncthreads();
       __builtin_amdgcn_sched_barrier(0);
       const char* nxt = smem + (kpar ^ 1) * STAGE;
-      if constexpr (next_up) read_up(fx0, nxt, I0{}, I0{});
-      else read_skip(fx0, nxt, I0{}, I0{});
+      if constexpr (next_up) read_up(fx[b], nxt, I0{}, I0{}, RAll{});
+      else read_skip(fx[b], nxt, I0{}, I0{}, RAll{});
+    } else if constexpr (tb == 2) {
+      read_skip(fx[b], cur, std::integral_constant<int, ta + 1>{}, I0{}, RAll{});
     } else {
-      read_skip(fx0, cur, std::integral_constant<int, tap + 1>{}, I0{});
+      read_skip(fx[b], cur, TA{}, std::integral_constant<int, tb + 2>{}, RFirst{});
     }
-    mfma_half(fx1, wq[tap % 3], I1{}, FIRST);
-    pin_half();
+    mfma_half(fx[b ^ 1], wq[tap % 3], I1{}, FIRST);
+    pin_half(PART_B{});
   };
   // One low-resolution pair (ty, tx) = two halves with their own weights (sets 2 (pair & 1), + 1); each half requests its counterpart of the
-  // next pair into the other pair of sets.  LAST (pair 3 only): the next chunk is the next tile's first skip chunk (taps 0 / 1 into sets 0 / 1).
+  // next pair into the other pair of sets.  Fragments, b = (3 ty + tx) & 1: half A uses set c = tx in fx[b] and reads set c + 1 into fx[b ^ 1]
+  // (all of it for tx = 0, else groups 2, 3); half B uses set c = tx + 1 in fx[b ^ 1] and reads into fx[b] groups 0, 1 of set 2 (tx = 0) or all
+  // of the next row's set 0 (tx = 1).  LAST (pair 3 only): the next chunk is the next tile's first skip chunk (taps 0 / 1 into sets 0 / 1).
   auto up_pair = [&](auto PAIR, int chunk, auto LAST) __attribute__((always_inline)) {
-    constexpr int pair = decltype(PAIR)::value;
+    constexpr int pair = decltype(PAIR)::value, ty = pair >> 1, tx = pair & 1, b = (3 * ty + tx) & 1;
     constexpr bool last = decltype(LAST)::value;
     constexpr int s0 = 2 * (pair & 1), n0s = 2 * ((pair + 1) & 1);
+    using TY = std::integral_constant<int, ty>;
+    using PART_A = std::conditional_t<tx == 0, RAll, RSecond>;
+    using PART_B = std::conditional_t<tx == 1, RAll, RFirst>;
     const char* cur = smem + kpar * STAGE;
-    read_up(fx1, cur, PAIR, I1{});
-    mfma_half(fx0, wq[s0], I0{}, std::false_type{});
+    read_up(fx[b ^ 1], cur, TY{}, std::integral_constant<int, tx + 1>{}, PART_A{});
+    mfma_half(fx[b], wq[s0], I0{}, std::false_type{});
     if constexpr (pair < 3) load_w_up(chunk, pair + 1, 0, std::integral_constant<int, n0s>{});
     else if constexpr (last) load_w_skip(0, 0, std::integral_constant<int, n0s>{});
     else load_w_up(chunk + 1, 0, 0, std::integral_constant<int, n0s>{});
-    pin_half_with_loads();
+    pin_half_with_loads(PART_A{});
     if constexpr (pair == 3) {
       __syncthreads();
       __builtin_amdgcn_sched_barrier(0);
       const char* nxt = smem + (kpar ^ 1) * STAGE;
-      if constexpr (last) read_skip(fx0, nxt, I0{}, I0{});
-      else read_up(fx0, nxt, I0{}, I0{});
+      if constexpr (last) read_skip(fx[b], nxt, I0{}, I0{}, RAll{});
+      else read_up(fx[b], nxt, I0{}, I0{}, RAll{});
+    } else if constexpr (tx == 1) {
+      read_up(fx[b], cur, std::integral_constant<int, ty + 1>{}, I0{}, RAll{});
     } else {
-      read_up(fx0, cur, std::integral_constant<int, pair + 1>{}, I0{});
+      read_up(fx[b], cur, TY{}, I2{}, RFirst{});
     }
-    mfma_half(fx1, wq[s0 + 1], I1{}, std::false_type{});
+    mfma_half(fx[b ^ 1], wq[s0 + 1], I1{}, std::false_type{});
     if constexpr (pair < 3) load_w_up(chunk, pair + 1, 1, std::integral_constant<int, n0s + 1>{});
     else if constexpr (last) load_w_skip(0, 1, std::integral_constant<int, n0s + 1>{});
     else load_w_up(chunk + 1, 0, 1, std::integral_constant<int, n0s + 1>{});
-    pin_half_with_loads();
+    pin_half_with_loads(PART_B{});
   };
   auto skip_chunk = [&](int chunk, auto FIRST, auto NEXT_UP) __attribute__((always_inline)) {
     skip_tap(std::integral_constant<int, 0>{}, chunk, FIRST, std::false_type{});
@@ -426,7 +454,7 @@ __global__ __launch_bounds__(THREADS, 1) void conv_up_kernel(UpArgs a) {
   load_w_skip(0, 0, std::integral_constant<int, 0>{});
   load_w_skip(0, 1, std::integral_constant<int, 1>{});
   __syncthreads();                                                     // stage 0 holds chunk 0 of the first tile; `epi` is written
-  read_skip(fx0, smem, I0{}, I0{});
+  read_skip(fx[0], smem, I0{}, I0{}, RAll{});
   for (int ti = 0; ti < owned; ++ti) {
     int bx = __builtin_amdgcn_readfirstlane(tile_of(wgx, ti, G, ngrp));
     const int tx = bx % a.tiles_x; bx /= a.tiles_x;

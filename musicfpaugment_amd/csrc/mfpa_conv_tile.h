@@ -1,4 +1,4 @@
-// What the MFMA convolution sources share: the vector types (csrc/unet.hip, unet_ws.hip, unet_up.hip), the "one MFMA, then k LDS reads"
+// What the MFMA convolution sources share: the vector types (csrc/unet.hip, unet_wd16.hip, unet_ws.hip, unet_up.hip), the "one MFMA, then k LDS reads"
 // scheduling pattern (also csrc/demucs.hip), the bf16 hi | lo split of the bf16x3 products, a compile-time index loop, and -- namespace
 // mfpa_tile::role_split -- the tile geometry and LDS plane layout of the two role-split kernels (conv_ws64_kernel, conv_up_kernel).
 #pragma once
@@ -44,14 +44,15 @@ __device__ __forceinline__ void split_bf16x3(f32x2 x, unsigned& hi, unsigned& lo
   lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
 }
 
-// f(integral_constant<int, FIRST>{}), ..., f(integral_constant<int, FIRST + N - 1>{}): straight-line code, the index a compile-time constant
-template <int FIRST, class F, int... I>
-__device__ __forceinline__ void each_index_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, FIRST + I>{}), ...);
+// f(integral_constant<int, FIRST>{}, a...), ..., f(integral_constant<int, FIRST + N - 1>{}, a...): straight-line code, the index a compile-time
+// constant
+template <int FIRST, class F, int... I, class... A>
+__device__ __forceinline__ void each_index_impl(F&& f, std::integer_sequence<int, I...>, A&&... a) {
+  (f(std::integral_constant<int, FIRST + I>{}, a...), ...);
 }
-template <int N, int FIRST = 0, class F>
-__device__ __forceinline__ void each_index(F&& f) {
-  each_index_impl<FIRST>(f, std::make_integer_sequence<int, N>{});
+template <int N, int FIRST = 0, class F, class... A>
+__device__ __forceinline__ void each_index(F&& f, A&&... a) {
+  each_index_impl<FIRST>(f, std::make_integer_sequence<int, N>{}, a...);
 }
 
 // conv_ws64_kernel (csrc/unet_ws.hip) and conv_up_kernel (csrc/unet_up.hip): 8 x 32 output tiles, 4 compute + 4 loader waves, two LDS stages

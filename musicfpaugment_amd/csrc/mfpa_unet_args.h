@@ -1,7 +1,9 @@
-// Kernel-side argument block of the UNet convolution kernels (csrc/unet.hip, csrc/unet_ws.hip); filled from mfpa_conv_desc (include/mfpa.h)
-// by mfpa_conv_mfma and the other entry points of unet.hip.
+// Kernel-side argument block of the UNet convolution kernels (csrc/unet.hip, csrc/unet_wd16.hip, csrc/unet_ws.hip); filled from mfpa_conv_desc
+// (include/mfpa.h) by mfpa_conv_mfma and the other entry points of unet.hip.  Below it: what unet.hip's routing needs from the kernels' own files.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "../../include/mfpa.h"
 
 namespace mfpa_unet {
 
@@ -70,5 +72,25 @@ __attribute__((visibility("hidden"))) bool conv_up_serves(int H, int W, int Hl, 
 template <bool C1SRC> __attribute__((visibility("hidden"))) int launch_conv_ws64(ConvArgs& a, hipStream_t s);     // <false> and <true> exist
 // does conv_ws64_kernel serve this ConvArgs (host arithmetic; asked by conv_route of csrc/unet.hip before it routes a launch there)?
 __attribute__((visibility("hidden"))) bool conv_ws64_serves(const ConvArgs& a);
+
+// csrc/unet_wd16.hip: the weights-direct 3x3 convolution conv_wd16_kernel<PH, PW, ROWS, WMW, SIDE, PLAIN, IN16, AFF16>.  Every instantiation that
+// exists, each template argument list written ONCE: unet_wd16.hip expands the list to the explicit instantiations of launch_wd16, CONV_KERNELS
+// (csrc/unet.hip) to the route entries.  128-channel tiles (WMW 2): a bf16 source always on the ROWS loop; 64-channel tiles (WMW 4): no ROWS loop.
+#define MFPA_WD16_FORMS(X)                                                                                                              \
+  X(8, 32, 0, 2, 0, 0, 0, 0) X(8, 32, 0, 2, 1, 0, 0, 0) X(8, 32, 1, 2, 0, 0, 0, 0) X(8, 32, 1, 2, 1, 0, 0, 0) X(8, 32, 0, 2, 0, 1, 0, 0)     \
+  X(8, 32, 0, 2, 1, 1, 0, 0) X(8, 32, 1, 2, 0, 1, 0, 0) X(8, 32, 1, 2, 1, 1, 0, 0) X(8, 32, 1, 2, 0, 1, 1, 0) X(8, 32, 1, 2, 1, 1, 1, 0)     \
+  X(8, 32, 1, 2, 1, 1, 1, 1)                                                                                                            \
+  X(16, 16, 0, 2, 0, 0, 0, 0) X(16, 16, 0, 2, 1, 0, 0, 0) X(16, 16, 1, 2, 0, 0, 0, 0) X(16, 16, 1, 2, 1, 0, 0, 0) X(16, 16, 0, 2, 0, 1, 0, 0) \
+  X(16, 16, 0, 2, 1, 1, 0, 0) X(16, 16, 1, 2, 0, 1, 0, 0) X(16, 16, 1, 2, 1, 1, 0, 0) X(16, 16, 1, 2, 0, 1, 1, 0) X(16, 16, 1, 2, 1, 1, 1, 0) \
+  X(16, 16, 1, 2, 1, 1, 1, 1)                                                                                                           \
+  X(8, 32, 0, 4, 0, 0, 0, 0) X(8, 32, 0, 4, 1, 0, 0, 0) X(8, 32, 0, 4, 0, 1, 0, 0) X(8, 32, 0, 4, 1, 1, 0, 0) X(8, 32, 0, 4, 0, 1, 1, 0)     \
+  X(8, 32, 0, 4, 1, 1, 1, 0) X(8, 32, 0, 4, 1, 1, 1, 1)
+// sizes LDS and the grid and launches that instantiation; rejects nothing (conv_route has).  Returns MFPA_OK / a HIP error code.
+template <int PH, int PW, bool ROWS, int WMW, bool SIDE, bool PLAIN, bool IN16, bool AFF16>
+__attribute__((visibility("hidden"))) int launch_wd16(ConvArgs& a, hipStream_t s);
+// the kernel's two shape rules that conv_route and mfpa_conv_stats_rows (csrc/unet.hip) apply: the ROWS loop form from this many input
+// channels up, and the tile (wmw, bn, ph, pw) of a (W, Cout)
+__attribute__((visibility("hidden"))) extern const int CONV_WD16_ROWS;
+__attribute__((visibility("hidden"))) void conv_wd16_tile(int W, int Cout, mfpa_conv_route* t);
 
 }  // namespace mfpa_unet

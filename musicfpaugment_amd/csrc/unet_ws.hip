@@ -1,7 +1,7 @@
 // Wave-specialised 3x3 convolution for the UNet's 64-channel full-resolution layers (training/unet.py:8-25 DoubleConv of `inc` and
 // `up4`; inference, bf16x3 products on v_mfma_f32_16x16x32_bf16).  Round 5.
 //
-// Why another kernel.  conv_wd16_kernel<.., WMW = 4> (csrc/unet.hip) gives these layers 8 waves that ALL do everything -- request the halo
+// Why another kernel.  conv_wd16_kernel<.., WMW = 4> (csrc/unet_wd16.hip) gives these layers 8 waves that ALL do everything -- request the halo
 // from HBM, split it into bf16 hi / lo planes in LDS, pull their weight fragments through the L1 and issue the MFMAs -- with the two
 // waves of a SIMD in barrier lock-step.  Vector-memory returns are in order, so a wave's wait for a weight fragment requested behind the
 // chunk's six HBM halo loads is a wait for HBM, and while it waits it issues no MFMA either; its SIMD-mate waits for the same thing.

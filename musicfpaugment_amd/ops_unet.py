@@ -1,4 +1,4 @@
-"""UNet building blocks over the C ABI (csrc/unet.hip): weight packing and the eval forward.
+"""UNet building blocks over the C ABI (csrc/unet.hip and the kernels' own files unet_wd16.hip, unet_ws.hip, unet_up.hip): weight packing and the eval forward.
 
 Activations are NHWC float32 tensors (B, H, W, C) -- H = frequency bins, W = frames.
 """
@@ -62,7 +62,7 @@ def frag_layout() -> int:
 
 def split_bf16x3_frag(w: torch.Tensor, layout: int = 2) -> torch.Tensor:
     """Kernel-layout fp32 weights [taps][Cout][Cin] (Cout % 16 == 0, Cin % 32 == 0) -> the FRAGMENT-ORDERED bf16x3 image of the
-    "weights direct" convolution kernels (mfpa_conv_desc.w_layout 2; v_mfma_f32_16x16x32_bf16 in conv_ws64_kernel / conv_wd16_kernel): a
+    "weights direct" convolution kernels (mfpa_conv_desc.w_layout 2; v_mfma_f32_16x16x32_bf16 in conv_ws64_kernel, csrc/unet_ws.hip, and conv_wd16_kernel, csrc/unet_wd16.hip): a
     wave reads the MFMA weight operand of a column tile as 1 KB contiguous pieces, one 16-byte fragment per lane.  Same split w = hi + lo
     as split_bf16x3.  [tap][chunk = Cin / 32][Cout / 16][hi | lo][lane 64][8 bf16], lane (g = l >> 4, c = l & 15) = output channel
     16 t + c, input channels 32 chunk + 8 g .. + 7.  Opaque float32 tensor of w's shape.  `layout` must be 2."""

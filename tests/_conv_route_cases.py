@@ -18,7 +18,8 @@ WD16_FORMS_WMW2 = [(0, 0, 0, 0, 0), (0, 1, 0, 0, 0), (1, 0, 0, 0, 0), (1, 1, 0, 
                    (1, 1, 1, 0, 0), (1, 0, 1, 1, 0), (1, 1, 1, 1, 0), (1, 1, 1, 1, 1)]
 WD16_FORMS_WMW4 = [(0, 0, 0, 0, 0), (0, 1, 0, 0, 0), (0, 0, 1, 0, 0), (0, 1, 1, 0, 0), (0, 0, 1, 1, 0), (0, 1, 1, 1, 0), (0, 1, 1, 1, 1)]
 
-# every instantiation the launcher's table (CONV_KERNELS, csrc/unet.hip) names: 2 + 29 + 27 + 8 = 66 kernels
+# every instantiation the launcher's table (CONV_KERNELS, csrc/unet.hip; the 29 wd16 forms from MFPA_WD16_FORMS, csrc/mfpa_unet_args.h) names:
+# 2 + 29 + 27 + 8 = 66 kernels
 KERNELS = (
     {("ws64", 0), ("ws64", 1)}
     | {("wd16", ph, pw, r, 2, s, p, i, a) for ph, pw in ((8, 32), (16, 16)) for r, s, p, i, a in WD16_FORMS_WMW2}

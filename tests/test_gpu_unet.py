@@ -167,7 +167,7 @@ def test_bf16x3_gate_on_stressed_and_trained_weight_families(family, trained_sd)
 
 
 def test_weights_direct_kernels_against_the_lds_staged_kernel():
-    """The "weights direct" bf16x3 convolutions (csrc/unet.hip: weight fragments from a fragment-ordered image straight into the MFMA
+    """The "weights direct" bf16x3 convolutions (csrc/unet_wd16.hip, csrc/unet_ws.hip: weight fragments from a fragment-ordered image straight into the MFMA
     operand registers, no weight tile in LDS, one barrier per chunk) against the pipelined kernel with LDS-staged weight tiles.
     conv_wd16_kernel (v_mfma_f32_16x16x32_bf16, w_layout 2) forms the same products but sums a 32-channel chunk inside one
     instruction: equal to fp32 rounding (<= 2e-6 of the largest output), bit-reproducible from run to run.  Ragged patch

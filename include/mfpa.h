@@ -260,6 +260,31 @@ int mfpa_audfprint_match(const uint32_t* table, const int32_t* counts, const int
                          int search_depth, int window, int max_alignments, long long hcap, void* scratch, int K, int32_t* out,
                          int32_t* info, void* stream);
 
+/* mfpa_audfprint_match_ex: the same matcher with exact_count, find_time_range and hashesfor (audfprint_match.py:131-233,
+ * :293-296, :343-349).  Arguments as mfpa_audfprint_match, and:
+ *   flags: 1 = exact_count (every local maximum of an id's dt histogram with count >= threshcount is a mode, dt ascending,
+ *          no max_alignments cap; filtered_count = distinct query_time + (hash << timebits) inside the window, computed in
+ *          64 bits with timebits = max(1, encpowerof2(largest query time that has a hit)); rows with count < threshcount
+ *          are dropped; needs threshcount >= 1), 2 = find_time_range (columns 5-6 = min_time, max_time: the sorted query
+ *          times mt of the window's hits, one per hit, at mt[int(n * q)] and mt[int(n * (1 - q)) - 1], -1 = the last);
+ *   time_quantile q in [0, 1);
+ *   pow2_roundup_mask: bit k set when numpy's float64 ceil(log(2^k) / log(2)) gives k + 1 (the caller computes it);
+ *   hashesfor >= 0: the sorted distinct packed values of result row `hashesfor` of each query, unpacked to
+ *          hf_out (B,hf_cap,2) int32 rows [packed & (2^timebits - 1), packed >> timebits]; hf_count (B) int32 = their
+ *          number, -1 when the query has no such row; when it exceeds hf_cap nothing is written (call again with more
+ *          room).  -1: no list, hf_out / hf_count are not read;
+ *   scratch: B * mfpa_audfprint_match_ex_scratch_bytes(hcap) bytes;  cap <= 32768.  A negative query
+ *   time packs as in the reference (int64 arithmetic).
+ * Ties of the filtered count: (orig_rank, mode order), mode order being dt ascending under flag 1.  With flags 0 and
+ * hashesfor -1 the result is mfpa_audfprint_match's.
+ */
+int mfpa_audfprint_match_ex_scratch_bytes(long long hcap, long long* bytes);
+int mfpa_audfprint_match_ex(const uint32_t* table, const int32_t* counts, const int32_t* hashesperid, int n_ids, int hashbits,
+                            int timebits, int depth, const int32_t* hashes, const int32_t* nq, int B, int cap, int threshcount,
+                            int search_depth, int window, int max_alignments, int flags, double time_quantile,
+                            uint32_t pow2_roundup_mask, int hashesfor, int hf_cap, int32_t* hf_out, int32_t* hf_count,
+                            long long hcap, void* scratch, int K, int32_t* out, int32_t* info, void* stream);
+
 /* Dejavu fingerprint store and matcher.  Integer only; results equal the reference's exactly.
  *
  * Table: (n_rows, 5) int32 rows [w0, w1, w2, song_id, offset], w0..w2 the 10-byte digest (sha1 hex[:20],

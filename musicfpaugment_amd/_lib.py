@@ -21,7 +21,7 @@ EINVAL = -22
 EHIP = -1000
 F32, F64 = 0, 1
 STFT_TABLE_LEN = 1288
-ABI_VERSION = 45
+ABI_VERSION = 46
 
 
 class MfpaError(RuntimeError):
@@ -64,6 +64,10 @@ _SIGNATURES = {
     "mfpa_audfprint_match_scratch_bytes": ([c_longlong, c_void_p], c_int),
     "mfpa_audfprint_match": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                               c_int, c_int, c_int, c_int, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "mfpa_audfprint_match_ex_scratch_bytes": ([c_longlong, c_void_p], c_int),
+    "mfpa_audfprint_match_ex": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                 c_int, c_int, c_int, c_int, c_int, c_double, c_uint, c_int, c_int, c_void_p, c_void_p,
+                                 c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_dejavu_store": ([c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p], c_int),
     "mfpa_dejavu_lookup": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),

@@ -1,13 +1,16 @@
 """Audfprint matcher on MI355X -- drop-in for afp/audfprint/audfprint_match.py (Matcher).
 
 ``match_batch`` is the batched hot path: B query hash lists in hashes_batch's layout -> the top k rows
-[id, filtered_count, time_offset, raw_count, orig_rank, 0, 0] of each, all on the device (mfpa_audfprint_match: hit
-gathering, per-id counts, candidate ranking, mode extraction and ordering in one kernel).  ``match_hashes``, ``match_file``
-and ``file_match_to_msgs`` keep the reference's signatures and results.  Ties of the filtered count, which the reference
+[id, filtered_count, time_offset, raw_count, orig_rank, min_time, max_time] of each, all on the device (hit gathering,
+per-id counts, candidate ranking, mode extraction and ordering in one kernel).  ``match_hashes``, ``match_file`` and
+``file_match_to_msgs`` keep the reference's signatures and results.  Ties of the filtered count, which the reference
 leaves to numpy's unstable argsort, are ordered by candidate rank, then mode order.
 
-exact_count and find_time_range raise NotImplementedError (the identification experiment uses neither, and there is no
-CPU fallback); sort_by_time and max_returns are host post-processing and behave as in the reference.
+The defaults run mfpa_audfprint_match.  exact_count (every local maximum of an id's offset histogram is a mode, counted
+by its distinct matching hashes), find_time_range with time_quantile (columns 5-6: where in the query the match lies)
+and ``match_hashes(..., hashesfor=k)`` (the matching hashes of result row k) run mfpa_audfprint_match_ex on the device;
+they take at most 32768 query rows.  sort_by_time and max_returns are host post-processing and
+behave as in the reference.
 """
 from __future__ import annotations
 
@@ -34,41 +37,45 @@ class Matcher(object):
         self.max_alignments_per_id = 100
         self.hit_capacity = 1 << 15           # scratch hits per query; grows (and stays grown) when a query needs more
 
-    def _check_supported(self) -> None:
-        if self.exact_count:
-            raise NotImplementedError("exact_count=True: only the approximate counts (_approx_match_counts) run on the device")
-        if self.find_time_range:
-            raise NotImplementedError("find_time_range=True is not implemented on the device")
-
-    def match_batch(self, ht: HashTable, uniq: torch.Tensor, counts: torch.Tensor, k: int = 1):
+    def match_batch(self, ht: HashTable, uniq: torch.Tensor, counts: torch.Tensor, k: int = 1, hashesfor: Optional[int] = None):
         """uniq (B, cap, 2) int32 (time, hash), counts (B,) -> (rows (B, k, 7) int32, info (B, 3) int32 = [n_hits, rows
-        written, rows in total]) on the device; a query with no rows has info[:, 1] == 0."""
-        self._check_supported()
+        written, rows in total]) on the device; a query with no rows has info[:, 1] == 0.  With hashesfor = r two more results: (B, n, 2) int32 [time, hash] rows of the
+        matching hashes of result row r and their number (B,) int32 per query (-1: no row r)."""
         dev = ht.table.device
-        rows, info, self.hit_capacity = ops.audfprint_match(
+        res = ops.audfprint_match(
             ht.table, ht.counts, ht.hashesperid_device(), uniq.to(dev, torch.int32), counts.to(dev, torch.int32), k=k,
             threshcount=self.threshcount, search_depth=self.search_depth, window=self.window,
-            max_alignments_per_id=self.max_alignments_per_id, hcap=self.hit_capacity, timebits=ht.maxtimebits)
-        return rows, info
+            max_alignments_per_id=self.max_alignments_per_id, hcap=self.hit_capacity, timebits=ht.maxtimebits,
+            exact_count=bool(self.exact_count), find_time_range=bool(self.find_time_range),
+            time_quantile=float(self.time_quantile), hashesfor=hashesfor)
+        self.hit_capacity = res[2]
+        return (res[0], res[1]) + tuple(res[3:])
 
     def match_hashes(self, ht: HashTable, hashes, hashesfor: Optional[int] = None) -> Tuple[Any, Any]:
-        """audfprint_match.py:322-346: every result row of one query, filtered count descending."""
-        self._check_supported()
-        if hashesfor is not None:
-            raise NotImplementedError("hashesfor (_unique_match_hashes) is not implemented on the device")
+        """audfprint_match.py:322-349: every result row of one query, filtered count descending, and with hashesfor = k the
+        (n, 2) [time, hash] rows of the matching hashes of row k (IndexError when there is no row k, as in the reference)."""
         q = np.asarray(hashes, dtype=np.int64).reshape(-1, 2).astype(np.int32)
         dev = ht.table.device
         uq = torch.from_numpy(q).to(dev).reshape(1, -1, 2)
         n = torch.tensor([q.shape[0]], dtype=torch.int32, device=dev)
         if q.shape[0] == 0:
+            if hashesfor is not None:
+                raise IndexError(f"hashesfor={hashesfor}: the query has no result rows")
             return np.zeros((0, 7), np.int32), None
         k = 64
         while True:
-            rows, info = self.match_batch(ht, uq, n, k=k)
-            total = int(info[0, 2])
+            res = self.match_batch(ht, uq, n, k=k, hashesfor=hashesfor)
+            total = int(res[1][0, 2])
             if total <= k:
-                return rows[0, :total].cpu().numpy(), None
+                break
             k = total
+        rows = res[0][0, :total].cpu().numpy()
+        if hashesfor is None:
+            return rows, None
+        count = int(res[3][0])
+        if count < 0:
+            raise IndexError(f"hashesfor={hashesfor}: the query has {total} result rows")
+        return rows, res[2][0, :count].cpu().numpy().astype(np.int64)
 
     def match_file(self, analyzer, ht: HashTable, filename: str) -> Tuple[Any, float, int]:
         q_hashes = analyzer.wavfile2hashes(filename)

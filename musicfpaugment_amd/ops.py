@@ -419,20 +419,38 @@ def audfprint_store(table: torch.Tensor, counts: torch.Tensor, rows: torch.Tenso
                                      ptr(table), ptr(counts), stream()), "mfpa_audfprint_store")
 
 
-def match_scratch_bytes(hcap: int) -> int:
+def match_scratch_bytes(hcap: int, extended: bool = False) -> int:
     n = ctypes.c_longlong(0)
-    check(lib().mfpa_audfprint_match_scratch_bytes(int(hcap), ctypes.addressof(n)), "mfpa_audfprint_match_scratch_bytes")
+    name = "mfpa_audfprint_match_ex_scratch_bytes" if extended else "mfpa_audfprint_match_scratch_bytes"
+    check(getattr(lib(), name)(int(hcap), ctypes.addressof(n)), name)
     return int(n.value)
+
+
+def pow2_roundup_mask() -> int:
+    """Bit k is set when encpowerof2(2^k) (audfprint_match.py:17-21: int(ceil(log(v) / log(2))) in numpy's float64) is
+    k + 1, not k; the extended matcher reproduces encpowerof2 on the device from this mask."""
+    mask = 0
+    for k in range(32):
+        if int(np.ceil(np.log(np.int64(1) << k) / np.log(2))) > k:
+            mask |= 1 << k
+    return mask
 
 
 def audfprint_match(table: torch.Tensor, counts: torch.Tensor, hashesperid: torch.Tensor, hashes: torch.Tensor,
                     nq: torch.Tensor, k: int = 1, threshcount: int = 5, search_depth: int = 100, window: int = 2,
                     max_alignments_per_id: int = 100, hcap: int = 1 << 15, timebits: int = 14,
-                    scratch_budget: int = 1 << 30) -> Tuple[torch.Tensor, torch.Tensor, int]:
-    """Matcher.match_hashes (audfprint_match.py:322-346, approximate counts) for B queries: hashes (B, cap, 2) int32
-    (time, hash) with nq (B,) valid rows each -> (rows (B, k, 7) int32 sorted by filtered count, info (B, 3) int32
-    [n_hits, rows written, rows in total], the hit capacity used).  A query with more hits than the scratch capacity is
-    reported by the kernel and the batch runs again with a capacity that holds it: nothing is truncated."""
+                    scratch_budget: int = 1 << 30, exact_count: bool = False, find_time_range: bool = False,
+                    time_quantile: float = 0.05, hashesfor: Optional[int] = None, hashes_cap: int = 2048,
+                    extended: Optional[bool] = None):
+    """Matcher.match_hashes (audfprint_match.py:322-346) for B queries: hashes (B, cap, 2) int32 (time, hash) with nq (B,)
+    valid rows each -> (rows (B, k, 7) int32 sorted by filtered count, info (B, 3) int32 [n_hits, rows written, rows in
+    total], the hit capacity used).  A query with more hits than the scratch capacity is reported by the kernel and the
+    batch runs again with a capacity that holds it: nothing is truncated.
+
+    exact_count, find_time_range (with time_quantile) and hashesfor go through mfpa_audfprint_match_ex (`extended` forces
+    that entry point, or the default one, regardless); they need cap <= 32768.  With hashesfor = r the
+    result has two more members: (B, n, 2) int32 rows [time, hash] of the matching hashes of result row r, and (B,) int32
+    their number per query (-1: the query has no row r); the buffer grows from hashes_cap until every list fits."""
     for t, name in ((table, "table"), (counts, "counts"), (hashesperid, "hashesperid"), (hashes, "hashes"), (nq, "nq")):
         require_gpu(t, name)
         if t.dtype != torch.int32:
@@ -441,31 +459,63 @@ def audfprint_match(table: torch.Tensor, counts: torch.Tensor, hashesperid: torc
     hashbits = nb.bit_length() - 1
     if hashes.dim() != 3 or hashes.shape[2] != 2 or nq.shape != (hashes.shape[0],):
         raise ValueError("hashes must be (B, cap, 2) and nq (B,)")
+    flags = (1 if exact_count else 0) | (2 if find_time_range else 0)
+    if extended is None:
+        extended = bool(flags) or hashesfor is not None
+    elif not extended and (flags or hashesfor is not None):
+        raise ValueError("exact_count, find_time_range and hashesfor need the extended entry point")
+    if exact_count and threshcount < 1:
+        raise ValueError("exact_count needs threshcount >= 1: with less, empty bins of the dt histogram would be modes")
+    if not 0.0 <= time_quantile < 1.0:
+        raise ValueError("time_quantile must lie in [0, 1)")
+    if hashesfor is not None and hashesfor < 0:
+        raise ValueError("hashesfor must be a row index >= 0")
     B, cap = hashes.shape[0], hashes.shape[1]
+    if extended and cap > 1 << 15:
+        raise ValueError(f"the extended matcher takes at most 32768 rows per query, not {cap}")
     dev = hashes.device
     out = torch.zeros((B, k, 7), dtype=torch.int32, device=dev)
     info = torch.zeros((B, 3), dtype=torch.int32, device=dev)
+    want_hashes = hashesfor is not None
+    hf = torch.zeros((B, hashes_cap, 2), dtype=torch.int32, device=dev) if want_hashes else None
+    hf_n = torch.full((B,), -1, dtype=torch.int32, device=dev) if want_hashes else None
+
+    def done():
+        if not want_hashes:
+            return out, info, hcap
+        return out, info, hcap, hf[:, :max(0, int(hf_n.max())) if B else 0], hf_n
+
     if B == 0:
-        return out, info, hcap
+        return done()
     hashes, nq = hashes.contiguous(), nq.contiguous()
+    p2mask = pow2_roundup_mask() if extended else 0
     while True:
-        per_q = match_scratch_bytes(hcap)
+        per_q = match_scratch_bytes(hcap, extended)
         chunk = max(1, min(B, scratch_budget // per_q))
         scratch = torch.empty(chunk * per_q, dtype=torch.uint8, device=dev)
         for s in range(0, B, chunk):
             e = min(B, s + chunk)
-            check(lib().mfpa_audfprint_match(ptr(table), ptr(counts), ptr(hashesperid), hashesperid.numel(), hashbits, timebits,
-                                             depth, ptr(hashes[s:e]), ptr(nq[s:e]), e - s, cap, threshcount, search_depth,
-                                             window, max_alignments_per_id, hcap, ptr(scratch), k, ptr(out[s:e]),
-                                             ptr(info[s:e]), stream()), "mfpa_audfprint_match")
+            head = (ptr(table), ptr(counts), ptr(hashesperid), hashesperid.numel(), hashbits, timebits, depth, ptr(hashes[s:e]),
+                    ptr(nq[s:e]), e - s, cap, threshcount, search_depth, window, max_alignments_per_id)
+            tail = (hcap, ptr(scratch), k, ptr(out[s:e]), ptr(info[s:e]), stream())
+            if extended:
+                check(lib().mfpa_audfprint_match_ex(*head, flags, float(time_quantile), p2mask, hashesfor if want_hashes else -1,
+                                                    hf.shape[1] if want_hashes else 0, ptr(hf[s:e]) if want_hashes else None,
+                                                    ptr(hf_n[s:e]) if want_hashes else None, *tail), "mfpa_audfprint_match_ex")
+            else:
+                check(lib().mfpa_audfprint_match(*head, *tail), "mfpa_audfprint_match")
         del scratch
         need = int(info[:, 0].max())
-        if need <= hcap:
-            return out, info, hcap
-        if need > 1 << 26:
-            raise ValueError(f"a query has {need} table hits: more than the matcher's limit of 2^26 per query")
-        while hcap < need:
-            hcap <<= 1
+        if need > hcap:
+            if need > 1 << 26:
+                raise ValueError(f"a query has {need} table hits: more than the matcher's limit of 2^26 per query")
+            while hcap < need:
+                hcap <<= 1
+            continue
+        if want_hashes and int(hf_n.max()) > hf.shape[1]:              # a list longer than the buffer: reported, run again
+            hf = torch.zeros((B, int(hf_n.max()), 2), dtype=torch.int32, device=dev)
+            continue
+        return done()
 
 
 # ----------------------------------------------------------------------------- Dejavu fingerprint store / matcher

@@ -905,7 +905,9 @@ int mfpa_scale_rows(const float* x, int B, int T, const float* factor, const uin
 /* AddBackgroundNoise.random_background (background_noise.py:64-141, non-mixup branch): out[b] (T samples) = the
  * concatenation of up to P slices bank[src[b*P+p] .. + len[b*P+p]) (len 0 ends the list; the lengths of one example sum
  * to T) of a device-resident noise bank, every slice RMS-normalised (x / (rms + 1e-8), utils.py:190-205) and the whole
- * RMS-normalised again.  The host draws scene / file / offset like the reference (python `random`). */
+ * RMS-normalised again.  The host draws scene / file / offset like the reference (python `random`).
+ * A list whose lengths sum to more than T is NOT detected: its last slice is written past the example's T samples.  `out`
+ * must hold B * T floats. */
 int mfpa_gather_background(const float* bank, const long long* src, const int* len, int B, int P, int T, float* out,
                            void* stream);
 /* AddBackgroundNoise (background_noise.py:183-215): y = x + rms(x)/10^(snr/20) * noise, then y /= max|y|.

@@ -155,6 +155,19 @@ int mfpa_audfprint_pick(const double* spec, const double* clip_max, int B, int F
                         const double* gauss, double a_dec, int maxpks, double* work, uint8_t* mask,
                         int32_t* npeaks, void* stream);
 
+/* The same for a whole track: Audfprint_peaks.find_peaks(d) without a denoiser on a file of any length
+ * (afp/audfprint/peak_extractor.py:236-311), up to 16384 frames -- what the 14 time bits of the hash table store without
+ * wrapping (afp/audfprint/hash_table.py:55).  The arithmetic of mfpa_audfprint_pick, value for value; the pruner keeps its event
+ * list in the caller's workspace instead of LDS, and the node sums of np.mean's tree are read at the stride their number asks for.
+ *   spec (B, F, T) float64, 141 <= F = R + 1 <= 257, R % 4 == 0, 1 <= T <= 16384;  clip_max (B) float64, the maxima of spec
+ *   logs   (B, T, F) float64 workspace (the log values, frame-major)
+ *   sums   (B, 2 * nchunks) float64 workspace, nchunks = ceil(F * T / 8192)
+ *   events B * (T * maxpks * (8 + 4) + 4 * (T + 2)) bytes of workspace, 8-byte aligned
+ *   gauss / a_dec / maxpks / mask / npeaks as for mfpa_audfprint_prune */
+int mfpa_audfprint_pick_track(const double* spec, const double* clip_max, int B, int F, int T, double pole,
+                              const double* gauss, double a_dec, int maxpks, double* logs, double* sums, void* events,
+                              uint8_t* mask, int32_t* npeaks, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Dejavu picker.  mfpa_dejavu_prepare: arr = scale*ln(max(a, max/1e6)) - mean with
  * a = psd / denom (fingerprint.py:68,78-79; scale = 10; mean_order as for mfpa_audfprint_prepare:
@@ -229,6 +242,18 @@ int mfpa_audfprint_landmarks(const uint8_t* mask, int B, int R, int T, int cap, 
                              int32_t* counts, void* stream);
 int mfpa_dejavu_hashes(const uint8_t* mask, int B, int F, int T, int cap, int peak_cap, int fan, int min_dt,
                        int max_dt, uint8_t* digests, int32_t* t1, int32_t* counts, void* stream);
+
+/* mfpa_audfprint_landmarks for a whole track (peaks2landmarks takes a list of any length, afp/audfprint/peak_extractor.py:313-346;
+ * landmarks2hashes :40-58; the duplicate removal of wavfile2hashes :443-460): the frames are cut into tiles of 256, each sorted on its
+ * own -- the key is time << 32 | hash, so the tiles in order are the sorted list.  Same outputs and the same [-1, -1] for a clip with
+ * more than 8 peaks in a frame or more than `cap` landmarks; what differs:
+ *   mask (B,R,T) uint8, R <= 256, R % 4 == 0, 1 <= T <= 16384;  cap >= 1, any size
+ *   tiles (B, ceil(T / 256), 2) int32 workspace
+ *   landmarks, hashes: both may be NULL and are then not written
+ *   mindt >= 0, 1 <= targetdt <= 256, targetdf >= 0, 1 <= maxpairs <= 4 */
+int mfpa_audfprint_landmarks_track(const uint8_t* mask, int B, int R, int T, int cap, int mindt, int targetdt,
+                                   int targetdf, int maxpairs, int32_t* tiles, int32_t* landmarks, int32_t* hashes,
+                                   int32_t* uniq, int32_t* counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Audfprint hash table and matcher (identification-rate experiment, testing/audfprint_exps.py:17-84).  Integer only, except

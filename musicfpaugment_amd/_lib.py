@@ -21,7 +21,7 @@ EINVAL = -22
 EHIP = -1000
 F32, F64 = 0, 1
 STFT_TABLE_LEN = 1288
-ABI_VERSION = 46
+ABI_VERSION = 47
 
 
 class MfpaError(RuntimeError):
@@ -45,6 +45,8 @@ _SIGNATURES = {
                               c_void_p], c_int),
     "mfpa_audfprint_pick": ([c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_double, c_int, c_void_p, c_void_p,
                              c_void_p, c_void_p], c_int),
+    "mfpa_audfprint_pick_track": ([c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_double, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_dejavu_prepare": ([c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_int, c_void_p, c_void_p], c_int),
     "mfpa_dejavu_prepare_f32": ([c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p], c_int),
     "mfpa_dejavu_prepare_f32_ex": ([c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_void_p], c_int),
@@ -57,6 +59,8 @@ _SIGNATURES = {
     "mfpa_psnr_stats": ([c_void_p, c_int, c_void_p, c_int, c_longlong, c_void_p, c_void_p], c_int),
     "mfpa_audfprint_landmarks": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p], c_int),
+    "mfpa_audfprint_landmarks_track": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_dejavu_hashes": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                             c_void_p, c_void_p], c_int),
     "mfpa_audfprint_store": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ulonglong, c_void_p,

@@ -32,12 +32,18 @@ def landmarks2hashes(landmarks_list) -> np.ndarray:
 
 class Audfprint_peaks(object):
     def __init__(self, params: Optional[Dict[str, Any]] = None, denoising: bool = False, denoising_model=None,
-                 unet=None, device="cuda", demucs=None, float32_log: str = "rounded") -> None:
-        """`float32_log` ("rounded" | "numpy"): the logarithm find_peaks takes of the UNet's float32 output (:265-276) -- "numpy" is
+                 unet=None, device="cuda", demucs=None, float32_log: str = "rounded", whole_tracks: bool = False) -> None:
+        """`whole_tracks` (default off: every call behaves and fails as without it): inputs of more than 1500 STFT frames, up to
+        16384 (the 14 time bits of the hash table), are picked and hashed by the track kernels (ops.audfprint_pick_track,
+        ops.audfprint_landmarks_track) with the results the reference gives for a file of that length; shorter inputs take the same
+        kernels as ever (un-denoised inputs of 1435 to 1500 frames, whose launch those kernels cannot hold, take the track kernels
+        too).  Not together with a denoiser.
+        `float32_log` ("rounded" | "numpy"): the logarithm find_peaks takes of the UNet's float32 output (:265-276) -- "numpy" is
         numpy's own float32 log bit for bit, the reference's arithmetic; "rounded" (the default) the float64 log rounded once to
         float32.  The un-denoised branch is float64 in the reference and is not affected."""
         ops._float32_log_code(float32_log)
         self.float32_log = float32_log
+        self.whole_tracks = bool(whole_tracks)
         params = afp_settings["audfprint"] if params is None else params
         self.density = params["density"]
         self.target_sr = params["samplerate"]
@@ -68,6 +74,27 @@ class Audfprint_peaks(object):
         else:
             self.unet, self.demucs = None, None
 
+    CLIP_MAX_FRAMES = 1500           # ops.audfprint_prune: the event list of a clip in LDS
+    PREPARE_MAX_FRAMES = 45 * 8192 // 257      # 1434: the float64 frame-major mfpa_audfprint_prepare keeps 2 KB of LDS per 8192-element chunk of
+                                               # np.mean's reduction beside its 66 KB of tiles; 46 chunks no longer fit a CU's 160 KB (the launch fails)
+
+    def _track_path(self, n_samples: int) -> bool:
+        """Whether an input of n_samples takes the track kernels: `whole_tracks` and more than 1500 frames -- or, without a denoiser,
+        more than the 1434 the clip kernels' launch can hold."""
+        frames = ops.stft_frames(int(n_samples))
+        if not self.whole_tracks:
+            return False
+        if frames <= self.CLIP_MAX_FRAMES:
+            return not self.denoising and frames > self.PREPARE_MAX_FRAMES
+        if frames > ops.TRACK_MAX_FRAMES:
+            raise ValueError(f"{n_samples} samples = {frames} STFT frames: whole tracks take at most {ops.TRACK_MAX_FRAMES} frames "
+                             f"({ops.TRACK_MAX_FRAMES * self.n_hop / self.target_sr:.0f} s), what the 14 time bits of the hash table "
+                             "store without wrapping")
+        if self.denoising:
+            raise NotImplementedError(f"{frames} STFT frames with a denoiser: whole tracks are fingerprinted without one (the database "
+                                      f"side of the experiment never denoises); denoised inputs take at most {self.CLIP_MAX_FRAMES} frames")
+        return True
+
     # ------------------------------------------------------------------ batched device path
     def find_peaks_batch(self, wav: torch.Tensor, want_spec: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(B, T) float32 on the GPU -> (mask (B,256,nF) uint8, npeaks (B,) int32, spec (B,257,nF)).
@@ -77,6 +104,11 @@ class Audfprint_peaks(object):
         (peak masks only, no denoiser): the normalised spectrogram is not materialised -- the division by the clip maximum
         happens inside the log / high-pass kernel, same float64 quotient -- and None is returned in its place.
         """
+        if self._track_path(wav.shape[-1]):
+            mag, cmax = ops.stft_mag(wav, torch.float64)
+            mask, npeaks = ops.audfprint_pick_track(mag, cmax, ops.audfprint_a_dec(self.density, self.n_hop), self.maxpksperframe,
+                                                    float(self.f_sd))
+            return mask, npeaks, (ops.normalize_(mag, cmax, per_clip=True) if want_spec else None)   # the same float64 quotient
         mag, cmax = ops.stft_mag(wav, torch.float64)
         a_dec = ops.audfprint_a_dec(self.density, self.n_hop)
         if self.unet is not None:
@@ -99,6 +131,7 @@ class Audfprint_peaks(object):
         """wavfile2peaks (peak_extractor.py:347-430) for waveforms already in memory: with denoising_model == "demucs" the
         WAVEFORM goes through the Demucs denoiser first (:369-376), then find_peaks; the UNet acts inside find_peaks."""
         if self.demucs is not None:
+            self._track_path(wav.shape[-1])                  # (raises for a track: Demucs is not run over minutes of audio)
             wav = self.demucs(wav)[:, 0].contiguous()
         return self.find_peaks_batch(wav)
 
@@ -138,6 +171,7 @@ class Audfprint_peaks(object):
         (peaks_mask, waveform, sgram) with get_masks_waveforms."""
         d = self._read_waveform(filename, self.target_sr)
         if self.demucs is not None:
+            self._track_path(len(d))                         # (raises for a track)
             d = self.demucs(d.reshape(1, -1).to(self.device))[0, 0].cpu()           # :369-376
         self.soundfiledur = len(d) / self.target_sr
         if shifts is None or shifts < 2:
@@ -153,6 +187,7 @@ class Audfprint_peaks(object):
         """peak_extractor.py:426-460: unique sorted (time, hash) rows of one file (the instance's `shifts`)."""
         d = self._read_waveform(filename, self.target_sr).reshape(1, -1).to(self.device)
         if self.demucs is not None:
+            self._track_path(d.shape[1])                     # (raises for a track)
             d = self.demucs(d)[:, 0].contiguous()
         self.soundfiledur = d.shape[1] / self.target_sr
         uq, n = self.hashes_batch(d)
@@ -175,6 +210,8 @@ class Audfprint_peaks(object):
         are merged before the duplicate removal (:406-424, :437-444); cap' = cap * shifts."""
         shifts = self.shifts if shifts is None else shifts
         if shifts is None or shifts < 2:
+            if self._track_path(wav.shape[-1]):
+                return self._track_hashes(wav)
             mask, _, _ = self.find_peaks_batch(wav)
             while True:
                 _, _, uniq, counts = ops.audfprint_landmarks(mask, cap, self.mindt, self.targetdt, self.targetdf,
@@ -189,12 +226,18 @@ class Audfprint_peaks(object):
         keys = []
         for s in range(shifts):
             shiftsamps = int(s / self.shifts * self.n_hop) if self.shifts and self.shifts > 1 else int(s / shifts * self.n_hop)
-            mask, _, _ = self.find_peaks_batch(wav[:, shiftsamps:].contiguous())
-            _, hs, _, counts = ops.audfprint_landmarks(mask, cap, self.mindt, self.targetdt, self.targetdf, self.maxpairsperpeak)
-            if bool((counts < 0).any()):
-                raise ValueError("landmark capacity exceeded: raise `cap` (the kernel's limit is 8192 landmarks per clip)")
+            shifted = wav[:, shiftsamps:].contiguous()
+            if self._track_path(shifted.shape[-1]):          # a track: its unique rows (the union below removes what the shifts share)
+                hs, n = self._track_hashes(shifted)
+                n = n[:, None]
+            else:
+                mask, _, _ = self.find_peaks_batch(shifted)
+                _, hs, _, counts = ops.audfprint_landmarks(mask, cap, self.mindt, self.targetdt, self.targetdf, self.maxpairsperpeak)
+                if bool((counts < 0).any()):
+                    raise ValueError("landmark capacity exceeded: raise `cap` (the kernel's limit is 8192 landmarks per clip)")
+                n = counts[:, :1]
             k = (hs[:, :, 0].to(torch.int64) << 32) + (hs[:, :, 1].to(torch.int64) & 0xFFFFFFFF)     # :447-449
-            valid = torch.arange(cap, device=wav.device)[None, :] < counts[:, :1]
+            valid = torch.arange(hs.shape[1], device=wav.device)[None, :] < n
             keys.append(torch.where(valid, k, torch.full_like(k, torch.iinfo(torch.int64).max)))
         k = torch.sort(torch.cat(keys, dim=1), dim=1).values                                           # np.sort(np.unique(.))
         first = torch.ones_like(k, dtype=torch.bool)
@@ -202,11 +245,21 @@ class Audfprint_peaks(object):
         first &= k != torch.iinfo(torch.int64).max
         n = first.sum(dim=1).to(torch.int32)
         pos = torch.cumsum(first.to(torch.int64), dim=1) - 1
-        out = torch.zeros((B, cap * shifts, 2), dtype=torch.int32, device=wav.device)
+        out = torch.zeros((B, k.shape[1], 2), dtype=torch.int32, device=wav.device)           # cap * shifts for clips
         b_idx = torch.arange(B, device=wav.device)[:, None].expand_as(k)
         out[b_idx[first], pos[first], 0] = (k[first] >> 32).to(torch.int32)
         out[b_idx[first], pos[first], 1] = (k[first] & 0xFFFFFFFF).to(torch.int32)
         return out, n
+
+    def _track_hashes(self, wav: torch.Tensor):
+        """hashes_batch (one shift) through the track kernels.  The capacity is maxpairsperpeak * the most peaks of a clip, an exact
+        upper bound at the cost of one sync: no retry."""
+        mask, npeaks, _ = self.find_peaks_batch(wav, want_spec=False)
+        cap = max(16, self.maxpairsperpeak * int(npeaks.max())) if wav.shape[0] else 16
+        _, _, uniq, counts = ops.audfprint_landmarks_track(mask, cap, self.mindt, self.targetdt, self.targetdf, self.maxpairsperpeak)
+        if bool((counts < 0).any()):
+            raise ValueError("more than 8 peaks in one frame: outside the device kernel's limits")
+        return uniq, counts[:, 1].contiguous()
 
     def peaks2landmarks(self, pklist: List[Tuple[int, int]]) -> List[Tuple[int, int, int, int]]:
         """[(col, bin)] -> [(col, bin1, bin2, dcol)], peak_extractor.py:313-346, through the device kernel."""

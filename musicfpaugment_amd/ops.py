@@ -246,6 +246,40 @@ def audfprint_pick(mag: torch.Tensor, clip_max: torch.Tensor, a_dec: Optional[fl
     return mask, npeaks
 
 
+TRACK_MAX_FRAMES = 16384          # HashTable keeps 14 time bits (hash_table.py:55 of the reference): frame times below 2^14 do not wrap
+
+
+def audfprint_pick_track(mag: torch.Tensor, clip_max: torch.Tensor, a_dec: Optional[float] = None, maxpks: int = AUDFPRINT_MAX_PKS,
+                         f_sd: float = AUDFPRINT_F_SD, pole: float = AUDFPRINT_POLE):
+    """audfprint_pick for whole tracks (mfpa_audfprint_pick_track): raw float64 |STFT| (B, F, T) with 1 <= T <= 16384 frames and its
+    per-clip maxima -> (mask (B, F-1, T) uint8, npeaks (B,) int32).  The same arithmetic, value for value; the pruner's event list
+    lives in a workspace allocated here (T * maxpks * 12 + 4 * (T + 2) bytes per clip) instead of LDS."""
+    require_gpu(mag, "spectrogram")
+    if mag.dim() != 3 or mag.dtype != torch.float64:
+        raise ValueError("spectrogram must be (B, F, T) float64")
+    mag = mag.contiguous()
+    B, F, T = mag.shape
+    if clip_max.shape != (B,) or clip_max.dtype != torch.float64:
+        raise ValueError("clip_max must be (B,) float64")
+    if F < 141 or F > 257 or (F - 1) % 4 or T < 1 or T > TRACK_MAX_FRAMES or not (1 <= maxpks <= 8):
+        raise ValueError(f"unsupported shape for the track picker (141 <= F <= 257, (F - 1) % 4 == 0, 1 <= T <= {TRACK_MAX_FRAMES}, "
+                         "maxpks <= 8)")
+    if a_dec is None:
+        a_dec = audfprint_a_dec()
+    dev = mag.device
+    gauss = gauss_table(F - 1, f_sd, dev)
+    nchunks = (F * T + 8191) // 8192
+    logs = torch.empty((B, T, F), dtype=torch.float64, device=dev)
+    sums = torch.empty((B, 2 * nchunks), dtype=torch.float64, device=dev)
+    events = torch.empty(max(1, (B * (T * maxpks * 12 + 4 * (T + 2)) + 7) // 8), dtype=torch.float64, device=dev)
+    mask = torch.empty((B, F - 1, T), dtype=torch.uint8, device=dev)
+    npeaks = torch.empty((B,), dtype=torch.int32, device=dev)
+    check(lib().mfpa_audfprint_pick_track(ptr(mag), ptr(clip_max), B, F, T, float(pole), ptr(gauss), float(a_dec), int(maxpks),
+                                          ptr(logs), ptr(sums), ptr(events), ptr(mask), ptr(npeaks), stream()),
+          "mfpa_audfprint_pick_track")
+    return mask, npeaks
+
+
 # ----------------------------------------------------------------------------- Dejavu picker
 DEJAVU_RADIUS = 10   # afp/dejavu/variables.py:19 PEAK_NEIGHBORHOOD_SIZE
 DEJAVU_AMP_MIN = 50  # testing/parameters.py:32
@@ -355,6 +389,30 @@ def audfprint_landmarks(mask: torch.Tensor, cap: int = 4096, mindt: int = 2, tar
     counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
     check(lib().mfpa_audfprint_landmarks(ptr(mask), B, R, T, cap, mindt, targetdt, targetdf, maxpairs, ptr(lm), ptr(hs),
                                          ptr(uq), ptr(counts), stream()), "mfpa_audfprint_landmarks")
+    return lm, hs, uq, counts
+
+
+def audfprint_landmarks_track(mask: torch.Tensor, cap: int, mindt: int = 2, targetdt: int = 63, targetdf: int = 31, maxpairs: int = 3,
+                              want_lists: bool = False):
+    """audfprint_landmarks for whole tracks (mfpa_audfprint_landmarks_track): peak masks (B, R, T) uint8 with T <= 16384 and any
+    capacity `cap` -> (landmarks (B,cap,4) | None, hashes (B,cap,2) | None, unique sorted hashes (B,cap,2), counts (B,2)); the two
+    list-order outputs only with `want_lists`.  counts is [-1, -1] for a clip with more than 8 peaks in a frame or more than `cap`
+    landmarks."""
+    require_gpu(mask, "mask")
+    if mask.dim() != 3 or mask.dtype != torch.uint8:
+        raise ValueError("mask must be (B, R, T) uint8")
+    mask = mask.contiguous()
+    B, R, T = mask.shape
+    if cap < 1 or R > 256 or R % 4 or T < 1 or T > TRACK_MAX_FRAMES:
+        raise ValueError(f"cap must be >= 1, R <= 256 with R % 4 == 0 and 1 <= T <= {TRACK_MAX_FRAMES}")
+    dev = mask.device
+    lm = torch.zeros((B, cap, 4), dtype=torch.int32, device=dev) if want_lists else None
+    hs = torch.zeros((B, cap, 2), dtype=torch.int32, device=dev) if want_lists else None
+    uq = torch.zeros((B, cap, 2), dtype=torch.int32, device=dev)
+    counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+    tiles = torch.empty((B, (T + 255) // 256, 2), dtype=torch.int32, device=dev)
+    check(lib().mfpa_audfprint_landmarks_track(ptr(mask), B, R, T, int(cap), mindt, targetdt, targetdf, maxpairs, ptr(tiles), ptr(lm),
+                                               ptr(hs), ptr(uq), ptr(counts), stream()), "mfpa_audfprint_landmarks_track")
     return lm, hs, uq, counts
 
 

@@ -93,45 +93,57 @@ def compute_peaks_metrics_files(queries_augmented, clean_dir: str, analyzer_no_d
 
 # ----------------------------------------------------------------------------- identification rate (audfprint_exps.py:17-84)
 MAX_TRACK_FRAMES = 1500          # the pruner's frame limit (ops.audfprint_prune): 1 + n_samples // 256 <= 1500, ~48 s at 8 kHz
+WHOLE_TRACK_FRAMES = ops.TRACK_MAX_FRAMES     # with whole_tracks=True: 16384 frames, ~8.7 min (the 14 time bits of the hash table)
+TRACK_BATCH_FRAMES = 131072      # frames of one device batch of whole tracks: float64 spectrogram + its log copy stay near 0.5 GB
 
 
-def _check_track_length(n_samples: int, what: str) -> None:
+def _check_track_length(n_samples: int, what: str, whole_tracks: bool = False) -> None:
     frames = 1 + n_samples // 256
+    if whole_tracks:
+        if frames > WHOLE_TRACK_FRAMES:
+            raise ValueError(f"{what}: {n_samples} samples = {frames} STFT frames; whole tracks take at most {WHOLE_TRACK_FRAMES} "
+                             f"frames ({WHOLE_TRACK_FRAMES * 256 / 8000:.0f} s at 8 kHz): the hash table keeps 14 time bits")
+        return
     if frames > MAX_TRACK_FRAMES:
         raise ValueError(f"{what}: {n_samples} samples = {frames} STFT frames; the device peak picker takes at most "
                          f"{MAX_TRACK_FRAMES} frames ({MAX_TRACK_FRAMES * 256 / 8000:.0f} s at 8 kHz) per clip, and the landmark "
                          "kernel at most 8192 landmarks: split longer tracks")
 
 
-def _database_analyzer(device):
+def _database_analyzer(device, whole_tracks: bool = False):
     from ..constants import afp_settings
-    a = Audfprint_peaks(afp_settings["audfprint"], device=device)
+    a = Audfprint_peaks(afp_settings["audfprint"], device=device, whole_tracks=whole_tracks)
     a.shifts = 1                                                     # audfprint_exps.py:20-21
     return a
 
 
 @torch.no_grad()
-def create_fp_database_batch(tracks, names, ht=None, analyzer: Audfprint_peaks = None, batch: int = 64, device=None):
+def create_fp_database_batch(tracks, names, ht=None, analyzer: Audfprint_peaks = None, batch: int = 64, device=None,
+                             whole_tracks: bool = False):
     """Fingerprint database of `tracks` (a (N, T) tensor or a sequence of 1-D waveforms of any lengths up to the limit
     above), stored under `names` in the given order.  Tracks are fingerprinted in batches of equal length on the device
     (hashes_batch with shifts = 1, as create_fp_database) and stored in file order with HashTable.store_batch.  Returns the
-    HashTable."""
+    HashTable.  `whole_tracks`: tracks of up to 16384 frames (~8.7 min) are taken whole (Audfprint_peaks(whole_tracks=True)),
+    at most max(1, 131072 // frames) of them in one device batch."""
     from ..afp.audfprint.hash_table import HashTable
     device = torch.device(device if device is not None else (analyzer.device if analyzer is not None else "cuda"))
-    analyzer = analyzer or _database_analyzer(device)
+    analyzer = analyzer or _database_analyzer(device, whole_tracks)
+    if whole_tracks and not analyzer.whole_tracks:
+        raise ValueError("whole_tracks=True needs an analyzer built with whole_tracks=True")
     ht = ht if ht is not None else HashTable(device=device)
     tracks = list(tracks)
     if len(tracks) != len(names):
         raise ValueError("one name per track")
     for i, t in enumerate(tracks):
-        _check_track_length(int(torch.as_tensor(t).shape[-1]), f"track {i} ({names[i]})")
+        _check_track_length(int(torch.as_tensor(t).shape[-1]), f"track {i} ({names[i]})", whole_tracks)
     by_len = {}
     for i, t in enumerate(tracks):
         by_len.setdefault(int(torch.as_tensor(t).shape[-1]), []).append(i)
     per_track = [None] * len(tracks)
-    for _, idx in sorted(by_len.items()):
-        for s in range(0, len(idx), batch):
-            chunk = idx[s:s + batch]
+    for n_samples, idx in sorted(by_len.items()):
+        step = min(batch, max(1, TRACK_BATCH_FRAMES // (1 + n_samples // 256))) if whole_tracks else batch
+        for s in range(0, len(idx), step):
+            chunk = idx[s:s + step]
             wav = torch.stack([torch.as_tensor(tracks[i], dtype=torch.float32).reshape(-1) for i in chunk]).to(device)
             uq, n = analyzer.hashes_batch(wav.contiguous(), shifts=1)
             for j, i in enumerate(chunk):
@@ -209,11 +221,12 @@ def accuracy_from_rows(rows: torch.Tensor, gt: torch.Tensor):
     return {"No Denoising": int(ok1.sum()) / N, "With Denoising": int(ok2.sum()) / N, "Mix Pipeline": int(mix.sum()) / N}
 
 
-def create_fp_database(files, dbpath: str, device=None) -> None:
-    """audfprint_exps.py:17-27: ingest every file (unreadable ones are reported and skipped), save to dbpath."""
+def create_fp_database(files, dbpath: str, device=None, whole_tracks: bool = False) -> None:
+    """audfprint_exps.py:17-27: ingest every file (unreadable ones are reported and skipped), save to dbpath.  `whole_tracks`: files of
+    up to 16384 frames are fingerprinted whole, as by the reference."""
     from ..afp.audfprint.hash_table import HashTable
     hash_tab = HashTable(device=device)
-    analyzer = _database_analyzer(hash_tab.device)
+    analyzer = _database_analyzer(hash_tab.device, whole_tracks)
     for filename in files:
         try:
             analyzer.ingest(hash_tab, filename)

@@ -310,6 +310,41 @@ int mfpa_audfprint_match_ex(const uint32_t* table, const int32_t* counts, const 
                             uint32_t pow2_roundup_mask, int hashesfor, int hf_cap, int32_t* hf_out, int32_t* hf_count,
                             long long hcap, void* scratch, int K, int32_t* out, int32_t* info, void* stream);
 
+/* Maintenance of the Audfprint hash table: HashTable.remove and HashTable.retrieve (afp/audfprint/hash_table.py:277-316).
+ * Same table, counts and accepted (hashbits, timebits, depth) as above.  With n = min(counts[b], depth), a MATCH is a slot
+ * j < n of bucket b whose (table[b][j] >> timebits) - 1, taken on the unsigned value, is in the requested set.
+ * INVARIANT: both are specified on tables in which every slot at or beyond min(counts[b], depth) is zero (what store, reset,
+ * load and the reference's save produce); behaviour on other tables is unspecified.
+ * flags: 0, or MFPA_MAINTAIN_FULL_ROWS to read all `depth` slots of every bucket instead of counts[b] first and the valid
+ * prefix alone (the same results under the invariant).
+ *
+ * mfpa_audfprint_remove: removes a SET of ids in one pass, in place.  in_set (n_ids) uint8, nonzero = remove the id;
+ *   removed (n_ids) int32 receives the matches of each id over the whole table (the call zeroes it first).  A bucket without
+ *   a match is left as it is, a counts[b] above depth included; in a bucket with one the other entries of the first n slots
+ *   move to the front in order, the rest of the row becomes zero and counts[b] the number kept (the entries the reservoir
+ *   dropped are forgotten, :289-290).  The result equals the reference's remove called once per id, in any order.
+ *   n_ids == 0 (the empty set): MFPA_OK, no launch.
+ *
+ * mfpa_audfprint_retrieve_count / mfpa_audfprint_retrieve: the (time, hash) rows of K distinct ids, concatenated in request
+ *   order; one id's rows are (table[b][j] & (2^timebits - 1), b) of every match, bucket ascending then slot ascending
+ *   (:309-315).  rank (n_ids) int32 = the request rank 0..K-1 of each requested id, -1 elsewhere (ids >= n_ids are not
+ *   requested); work: mfpa_audfprint_retrieve_work_ints(hashbits, K) int32, carried from the first call to the second.
+ *   _count fills offsets (K + 1) int32: rows of rank k are [offsets[k], offsets[k + 1]); the caller reads offsets[K], sizes
+ *   rows (n_rows, 2) int32 and calls mfpa_audfprint_retrieve once (it consumes `work`).  Positions come from counts and
+ *   scans, never from the arrival order of atomics: the output is deterministic.  Needs depth * 2^hashbits < 2^31.
+ *   K == 0 (and n_rows == 0): MFPA_OK, no launch.
+ */
+#define MFPA_MAINTAIN_FULL_ROWS 1
+int mfpa_audfprint_remove(uint32_t* table, int32_t* counts, int hashbits, int timebits, int depth, const uint8_t* in_set,
+                          int n_ids, int flags, int32_t* removed, void* stream);
+int mfpa_audfprint_retrieve_work_ints(int hashbits, int K, long long* ints);
+int mfpa_audfprint_retrieve_count(const uint32_t* table, const int32_t* counts, int hashbits, int timebits, int depth,
+                                  const int32_t* rank, int n_ids, int K, int flags, int32_t* work, int32_t* offsets,
+                                  void* stream);
+int mfpa_audfprint_retrieve(const uint32_t* table, const int32_t* counts, int hashbits, int timebits, int depth,
+                            const int32_t* rank, int n_ids, int K, int flags, int32_t* work, const int32_t* offsets,
+                            int32_t* rows, int n_rows, void* stream);
+
 /* Dejavu fingerprint store and matcher.  Integer only; results equal the reference's exactly.
  *
  * Table: (n_rows, 5) int32 rows [w0, w1, w2, song_id, offset], w0..w2 the 10-byte digest (sha1 hex[:20],

@@ -72,6 +72,12 @@ _SIGNATURES = {
     "mfpa_audfprint_match_ex": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                  c_int, c_int, c_int, c_int, c_int, c_double, c_uint, c_int, c_int, c_void_p, c_void_p,
                                  c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "mfpa_audfprint_remove": ([c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p], c_int),
+    "mfpa_audfprint_retrieve_work_ints": ([c_int, c_int, c_void_p], c_int),
+    "mfpa_audfprint_retrieve_count": ([c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p], c_int),
+    "mfpa_audfprint_retrieve": ([c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_int, c_void_p], c_int),
     "mfpa_dejavu_store": ([c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p], c_int),
     "mfpa_dejavu_lookup": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),

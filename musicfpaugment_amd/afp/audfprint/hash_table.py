@@ -6,6 +6,10 @@ for the matcher.  ``store`` / ``store_batch`` run mfpa_audfprint_store: slots ar
 and a full bucket's reservoir slot comes from a counter-based draw keyed by (seed, bucket, arrival index) instead of
 Python's global `random`, so two ingests of the same input give the same table.
 
+``remove`` / ``remove_batch`` and ``retrieve`` / ``retrieve_batch`` (hash_table.py:277-316) run on the device too
+(mfpa_audfprint_remove, mfpa_audfprint_retrieve): one pass over the table for any number of tracks, the table never leaves the
+device, results equal the reference's bit for bit.
+
 ``save`` writes the reference's gzip-pickle layout under the class path ``afp.audfprint.hash_table.HashTable`` (the
 reference loads it), ``load`` reads a file the reference's ``HashTable.save`` wrote.
 """
@@ -232,11 +236,54 @@ class HashTable(object):
         self._hpid_dev = None
         self.dirty = True
 
-    def remove(self, name):
-        raise NotImplementedError("HashTable.remove is not part of the device table (rebuild the table without the track)")
+    # ------------------------------------------------------------------ maintenance
+    def _known_id(self, name: Union[int, str]) -> int:
+        """name_to_id without adding: an unknown name raises ValueError, an integer id outside the names list IndexError
+        (the reference's names[id_])."""
+        id_ = self.name_to_id(name)
+        if not 0 <= id_ < len(self.names):
+            raise IndexError(f"id {id_} is not in the table's {len(self.names)} ids")
+        return id_
 
-    def retrieve(self, name):
-        raise NotImplementedError("HashTable.retrieve is not part of the device table")
+    def remove(self, name: Union[int, str]) -> None:
+        """hash_table.py:277-295: drop every entry of the track and free its id (the next new name takes it)."""
+        self.remove_batch([name])
+
+    def remove_batch(self, names) -> List[int]:
+        """`remove` of every name (or integer id) of the list in ONE pass over the table -> the entries each one had.  The
+        table, counts, names and hashesperid are what the reference's remove, called once per name, leaves."""
+        names = list(names)
+        ids = [self._known_id(n) for n in names]
+        removed = ops.audfprint_remove(self.table, self.counts, sorted(set(ids)), len(self.names), self.maxtimebits)
+        removed = removed.cpu().tolist() if ids else []
+        for id_ in ids:
+            self.names[id_] = None
+            self.hashesperid[id_] = 0
+        self._hpid_dev = None
+        self.dirty = True
+        out = [removed[id_] for id_ in ids]
+        for name, n in zip(names, out):
+            print("Removed", name, "(", n, "hashes).")
+        return out
+
+    def retrieve(self, name: Union[int, str]) -> np.ndarray:
+        """hash_table.py:297-316: the (time, hash) rows the table holds of the track, (n, 2) int32, by hash then slot."""
+        return self.retrieve_batch([name])[0]
+
+    def retrieve_batch(self, names, on_device: bool = False):
+        """`retrieve` of every name (or integer id) of the list in one count and one scatter pass -> a list of (n, 2) int32
+        arrays; with on_device, (rows (N, 2), offsets (len(names) + 1,)) int32 tensors instead: rows[offsets[k]:offsets[k + 1]]
+        are names[k]'s (the names must then be distinct)."""
+        ids = [self._known_id(n) for n in names]
+        uniq = sorted(set(ids))
+        if on_device:
+            if len(uniq) != len(ids):
+                raise ValueError("retrieve_batch(on_device=True) needs distinct names")
+            return ops.audfprint_retrieve(self.table, self.counts, ids, self.maxtimebits)
+        rows, offsets = ops.audfprint_retrieve(self.table, self.counts, uniq, self.maxtimebits)
+        rows, offsets = rows.cpu().numpy(), offsets.cpu().numpy()
+        at = {id_: k for k, id_ in enumerate(uniq)}
+        return [rows[offsets[at[id_]]:offsets[at[id_] + 1]].copy() for id_ in ids]
 
     def list(self, print_fn: Optional[Callable[[str], None]] = None) -> None:
         print_fn = print_fn or print

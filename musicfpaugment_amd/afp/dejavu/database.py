@@ -9,7 +9,8 @@ order or the batching of the inserts.
 
 Postgres semantics kept: song ids count 1, 2, ... in insertion order and are never reused until `empty()`; duplicate rows
 are dropped (ON CONFLICT DO NOTHING); `setup()` deletes the songs never marked fingerprinted together with their rows
-(DELETE_UNFINGERPRINTED and the ON DELETE CASCADE).  The connection options of the reference's config are not used.
+(DELETE_UNFINGERPRINTED and the ON DELETE CASCADE), `delete_songs_by_id` the songs it is given in the same way.  The
+connection options of the reference's config are not used.
 
 `save` / `load` use a plain .npz (no pickle).  `insert_batch` / `match_batch` are the batched device forms.
 """
@@ -62,7 +63,11 @@ class DeviceDatabase(object):
         self._pending: List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = []
 
     def delete_unfingerprinted_songs(self) -> None:
-        gone = [sid for sid, s in self._songs.items() if not s["fingerprinted"]]
+        self._delete_songs([sid for sid, s in self._songs.items() if not s["fingerprinted"]])
+
+    def _delete_songs(self, gone: List[int]) -> None:
+        """DELETE FROM songs WHERE song_id IN (gone), and the ON DELETE CASCADE of their fingerprints: the rows that stay are
+        placed again by the store, so the table's bytes are those of a database that never held the songs."""
         if not gone:
             return
         for sid in gone:
@@ -111,7 +116,11 @@ class DeviceDatabase(object):
         raise NotImplementedError("dumping every fingerprint is not on the experiment's path: save() writes the table")
 
     def delete_songs_by_id(self, song_ids, batch_size: int = 1000) -> None:
-        raise NotImplementedError("deleting fingerprinted songs is not on the experiment's path: empty() clears the database")
+        """DELETE_SONGS (postgres_database.py:231-245, :362-364) with the cascade to the fingerprints.  Ids the songs table
+        does not hold are ignored, as by SQL's IN; deleted ids are not handed out again (song_id is SERIAL).  batch_size only
+        splits the reference's statement: here the whole list is one pass."""
+        gone = sorted({int(s) for s in song_ids} & set(self._songs))
+        self._delete_songs(gone)
 
     def insert_hashes(self, song_id: int, hashes, batch_size: int = 1000) -> None:
         """INSERT_FINGERPRINT ... ON CONFLICT DO NOTHING for every (hash hex, offset) (postgres_database.py:156-178)."""

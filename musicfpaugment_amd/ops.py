@@ -576,6 +576,83 @@ def audfprint_match(table: torch.Tensor, counts: torch.Tensor, hashesperid: torc
         return done()
 
 
+MAINTAIN_FULL_ROWS = 1          # MFPA_MAINTAIN_FULL_ROWS
+
+
+def _maintain_table(table: torch.Tensor, counts: torch.Tensor):
+    for t, name in ((table, "table"), (counts, "counts")):
+        require_gpu(t, name)
+        if t.dtype != torch.int32:
+            raise TypeError(f"{name} must be int32")
+    if table.dim() != 2:
+        raise ValueError("table must be (2^hashbits, depth)")
+    nb, depth = table.shape
+    hashbits = nb.bit_length() - 1
+    if nb != 1 << hashbits or counts.shape != (nb,):
+        raise ValueError("table must have 2^hashbits rows and counts one entry per row")
+    return hashbits, depth
+
+
+def _maintain_ids(ids, limit: Optional[int]) -> np.ndarray:
+    a = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+    if a.size and a.dtype.kind not in "iu":
+        raise TypeError("ids must be integers")
+    a = a.astype(np.int64).reshape(-1)
+    if a.size and (int(a.min()) < 0 or (limit is not None and int(a.max()) >= limit)):
+        raise ValueError("ids must lie in [0, n_ids)" if limit is not None else "ids must not be negative")
+    return a
+
+
+def audfprint_remove(table: torch.Tensor, counts: torch.Tensor, ids, n_ids: int, timebits: int = 14,
+                     full_rows: bool = False) -> torch.Tensor:
+    """HashTable.remove (hash_table.py:277-295) of a SET of ids in one pass over the table, in place -> removed (n_ids,)
+    int32, the entries each id had.  The same table and counts as the reference's remove called once per id, in any order
+    (mfpa_audfprint_remove; tables whose slots at or beyond min(counts, depth) are zero).  ids: integers in [0, n_ids)."""
+    hashbits, depth = _maintain_table(table, counts)
+    n_ids = int(n_ids)
+    if n_ids < 0:
+        raise ValueError("n_ids must not be negative")
+    a = _maintain_ids(ids, n_ids)
+    removed = torch.zeros(n_ids, dtype=torch.int32, device=table.device)
+    if a.size == 0:
+        return removed
+    in_set = np.zeros(n_ids, np.uint8)
+    in_set[a] = 1
+    in_set = torch.from_numpy(in_set).to(table.device)
+    check(lib().mfpa_audfprint_remove(ptr(table), ptr(counts), hashbits, int(timebits), depth, ptr(in_set), n_ids,
+                                      MAINTAIN_FULL_ROWS if full_rows else 0, ptr(removed), stream()), "mfpa_audfprint_remove")
+    return removed
+
+
+def audfprint_retrieve(table: torch.Tensor, counts: torch.Tensor, ids, timebits: int = 14, full_rows: bool = False):
+    """HashTable.retrieve (hash_table.py:297-316) of K distinct ids -> (rows (N, 2) int32 (time, hash) of all of them in
+    request order, each id's by bucket then slot; offsets (K + 1,) int32: rows[offsets[k]:offsets[k + 1]] are ids[k]'s).
+    Both stay on the device; the table is never copied, one integer (N) is read back to size `rows`."""
+    hashbits, depth = _maintain_table(table, counts)
+    a = _maintain_ids(ids, None)
+    K = int(a.size)
+    dev = table.device
+    if len(np.unique(a)) != K:
+        raise ValueError("ids must be distinct")
+    if K == 0:
+        return torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    n_ids = int(a.max()) + 1
+    rank = np.full(n_ids, -1, np.int32)
+    rank[a] = np.arange(K, dtype=np.int32)
+    rank = torch.from_numpy(rank).to(dev)
+    n = ctypes.c_longlong(0)
+    check(lib().mfpa_audfprint_retrieve_work_ints(hashbits, K, ctypes.addressof(n)), "mfpa_audfprint_retrieve_work_ints")
+    work = torch.empty(int(n.value), dtype=torch.int32, device=dev)
+    offsets = torch.empty(K + 1, dtype=torch.int32, device=dev)
+    flags = MAINTAIN_FULL_ROWS if full_rows else 0
+    head = (ptr(table), ptr(counts), hashbits, int(timebits), depth, ptr(rank), n_ids, K, flags, ptr(work), ptr(offsets))
+    check(lib().mfpa_audfprint_retrieve_count(*head, stream()), "mfpa_audfprint_retrieve_count")
+    n_rows = int(offsets[K])
+    rows = torch.empty((n_rows, 2), dtype=torch.int32, device=dev)
+    check(lib().mfpa_audfprint_retrieve(*head, ptr(rows), n_rows, stream()), "mfpa_audfprint_retrieve")
+    return rows, offsets
+
+
 # ----------------------------------------------------------------------------- Dejavu fingerprint store / matcher (DESIGN.md §3.9)
 DEJAVU_MAX_SID = (1 << 24) - 1        # song ids are packed into 24 bits of the matcher's sort key
 DEJAVU_DIRBITS = 20

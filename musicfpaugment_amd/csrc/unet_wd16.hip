@@ -838,9 +838,11 @@ int launch_wd16(ConvArgs& a, hipStream_t s) {
                      (a.w1x1 ? G::RED * sizeof(float) : 0);                                // + the fused OutConv's partial sums
   dim3 grid((unsigned)((long long)a.tiles_x * a.tiles_y * a.B), (unsigned)(a.Cout / wd16_bn(WMW)));
   if constexpr (wd16_persist(ROWS, WMW, SIDE, PLAIN)) {                // one workgroup per CU (and output-channel tile) walks the tiles
+    // ... where the chunk count is even: the halo stage of a chunk is (chunk & 1), so the next tile's chunk 0, split behind this tile's last
+    // chunk, lands in stage 0 only then.  An odd count (C_in % 64 == 32: the tap-by-tap WMW = 2 forms alone take it) keeps one tile per workgroup.
     const int cus = mfpa_current_device_cus();
     const unsigned per = (unsigned)((cus > 0 ? cus : 256) / (int)grid.y);
-    if (per >= 1 && grid.x > per) grid.x = per;
+    if (per >= 1 && grid.x > per && ((a.C0 + a.C1) / KC) % 2 == 0) grid.x = per;
   }
   hipLaunchKernelGGL((conv_wd16_kernel<PH, PW, ROWS, WMW, SIDE, PLAIN, IN16, AFF16>), grid, dim3(G::THREADS), lds, s, a);
   MFPA_CHECK_LAUNCH();

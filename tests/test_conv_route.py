@@ -32,6 +32,47 @@ def test_case_table_names_every_instantiation(lib):
     assert len(rc.KERNELS) == 66
 
 
+def test_exact_case_table_routes(lib):
+    """The table of tests/test_gpu_conv_exact.py: every row gets the instantiation it names (a routing change that moves a case to another
+    kernel fails here, without a GPU), the per-instantiation group alone reaches all 66, every walk case is a persistent kernel with
+    2 G < tiles < 3 G and a period that does not divide G, and the walk group holds every persistent form."""
+    groups = rc.exact_cases(cus=256)
+    assert sorted(groups) == ["epi", "inst", "pair", "walk"]
+    seen = {g: set() for g in groups}
+    names = set()
+    for group, rows in groups.items():
+        for name, fields, want in rows:
+            assert (group, name) not in names, (group, name)
+            names.add((group, name))
+            code, got, r = rc.route(lib, rc.desc(lib, **fields))
+            assert code == 0 and got == want, (group, name, code, got, want)
+            seen[group].add(got)
+            if group != "walk":
+                assert fields["B"] == 2, (group, name)
+    assert seen["inst"] == rc.KERNELS and len(rc.KERNELS) == 66, (sorted(rc.KERNELS - seen["inst"]), sorted(seen["inst"] - rc.KERNELS))
+    assert set().union(*seen.values()) == rc.KERNELS
+    # the per-instantiation rows are ragged against their patch in both directions, and cover two clips
+    for name, fields, want in groups["inst"]:
+        ph, pw = rc.patch(want)
+        assert fields["H"] % ph and fields["W"] % pw and fields.get("C1", 0) == 0, name
+    # two sources everywhere in `pair`, with a smaller second source
+    for name, fields, want in groups["pair"]:
+        assert fields["C1"] > 0 and fields["H1"] < fields["H"] and fields["W1"] < fields["W"], name
+    assert {(f["H"] - f["H1"], f["W"] - f["W1"]) for _, f, _ in groups["pair"]} == {(1, 1), (3, 2), (5, 2)}
+    persistent = {k for k in rc.KERNELS if rc.walks(k)}
+    assert len(persistent) == 25                                           # 2 ws64 + 7 WMW 4 + 14 PLAIN at WMW 2 + the 2 plain-loop taps forms
+    assert seen["walk"] == persistent, sorted(persistent - seen["walk"])
+    for name, fields, want in groups["walk"]:
+        assert want[0] == "ws64" or rc.wd16_persist(want[3], want[4], want[5], want[6]), name
+        _, _, r = rc.route(lib, rc.desc(lib, **fields))
+        G = 256 // (fields.get("Cout", 64) // r.bn)
+        per_clip = -(-fields["H"] // r.ph) * -(-fields["W"] // r.pw)
+        B, P = rc.walk_batch(G, per_clip)
+        assert B == fields["B"] and B % P == 0 and 2 * G < B * per_clip < 3 * G and G % (per_clip * P) != 0, (name, G, B, P)
+    assert rc.walk_batch(256, 4) == (162, 3) and rc.walk_batch(256, 2) == (321, 3)
+    assert rc.walk_batch(240, 4) == (154, 7)                                # 240 % 12 == 0 and 240 % 20 == 0: the period after those
+
+
 def test_route_fields(lib):
     """The fields that name no template parameter: channels per workgroup, rows of stats_part per tile, the no-op, the optional out."""
     h = lib.lib()

@@ -771,7 +771,8 @@ typedef struct mfpa_gemm_desc {
 int mfpa_gemm_mfma(const mfpa_gemm_desc* d, void* stream);
 /* The kernel mfpa_gemm_mfma would launch for `d`, host arithmetic only (no device is touched, nothing is launched): MFPA_EINVAL
  * exactly where mfpa_gemm_mfma returns it, otherwise MFPA_OK with *kernel_id (may be NULL) = one of the ids below;
- * MFPA_GEMM_NONE for the no-ops batch == 0 / M == 0.  mfpa_gemm_mfma itself dispatches on this id. */
+ * MFPA_GEMM_NONE for the no-ops batch == 0 / M == 0.  mfpa_gemm_mfma itself looks this id up in its
+ * launch table (GEMM_KERNELS, csrc/demucs_gemm.hip). */
 enum {
   MFPA_GEMM_NONE = -1,
   MFPA_GEMM_PIPE = 0,          /* gemm_bf16x3_pipe_kernel<false>: 256 x 128 tile, K % 64 == 0, K >= 128, npad % 128 == 0, M >= 192 */

@@ -2,8 +2,8 @@
 // Reference: training/train.py:275-312 (input_type == "audio": L1 + MultiResolutionSTFTLoss, loss.backward(), Adam) over
 // training/model.py:163-326.  torch autograd is not used: every layer's adjoint is written out.
 //
-// Activations are time-major (B, L, C) like the forward (csrc/demucs.hip).  Input gradients of every Conv1d /
-// ConvTranspose1d / 1x1 / LSTM projection are again strided-window GEMMs served by mfpa_gemm_mfma (a Conv1d's input
+// Activations are time-major (B, L, C) like the forward (csrc/demucs.hip, csrc/demucs_gemm.hip).  Input gradients of every Conv1d /
+// ConvTranspose1d / 1x1 / LSTM projection are again strided-window GEMMs served by mfpa_gemm_mfma (csrc/demucs_gemm.hip; a Conv1d's input
 // gradient is a ConvTranspose1d of the output gradient and vice versa); its epilogue applies the ReLU mask of the layer
 // below (mode 3).  The LSTM's backward recurrence is csrc/lstm.hip.  This file holds what else that kernel cannot express:
 //   gemm_tn_kernel        weight gradients  dW[m][n] += sum_rows dY[row][m] * Xwin[row][n]  (K = every time step of the batch)

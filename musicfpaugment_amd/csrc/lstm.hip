@@ -1,6 +1,6 @@
 // The LSTM recurrence of the Demucs denoiser for MI355X (gfx950), forward and backward -- torch.nn.LSTM of training/model.py:91-110
 // of deezer/musicFPaugment: two layers, unidirectional, zero initial state.  The input projections of all steps are one GEMM
-// (csrc/demucs.hip); this file holds the recurrence, in both directions as one persistent launch per layer and time range or, where
+// (mfpa_gemm_mfma, csrc/demucs_gemm.hip); this file holds the recurrence, in both directions as one persistent launch per layer and time range or, where
 // that grid cannot be resident, as one launch per time step:
 //   lstm_step_kernel<MT>           forward step:  gates = h[t-1] W_hh^T + xp[t], then the cell update
 //   lstm_seq_kernel<KS, MS>        forward range: W_hh in registers, h exchanged between workgroups in split form

@@ -1,5 +1,5 @@
 // What the MFMA convolution sources share: the vector types (csrc/unet.hip, unet_wd16.hip, unet_ws.hip, unet_up.hip), the "one MFMA, then k LDS reads"
-// scheduling pattern (also csrc/demucs.hip), the bf16 hi | lo split of the bf16x3 products, a compile-time index loop, and -- namespace
+// scheduling pattern (also csrc/demucs_gemm.hip, with the vector types; csrc/lstm.hip and csrc/demucs_train.hip take the types too), the bf16 hi | lo split of the bf16x3 products, a compile-time index loop, and -- namespace
 // mfpa_tile::role_split -- the tile geometry and LDS plane layout of the two role-split kernels (conv_ws64_kernel, conv_up_kernel).
 #pragma once
 #include <hip/hip_runtime.h>

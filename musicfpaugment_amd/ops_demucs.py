@@ -1,4 +1,4 @@
-"""Demucs forward over the C ABI (csrc/demucs.hip, the LSTM recurrence csrc/lstm.hip): weight packing and the layer schedule.
+"""Demucs forward over the C ABI (csrc/demucs.hip, the GEMM family and the fused end levels csrc/demucs_gemm.hip, the LSTM recurrence csrc/lstm.hip): weight packing and the layer schedule.
 
 Reference: Demucs.forward, training/model.py:290-326.  Activations are (B, L, C) float32 tensors."""
 from __future__ import annotations

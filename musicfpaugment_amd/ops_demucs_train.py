@@ -65,7 +65,7 @@ def colsum(x: int, rows, C, ld, out: torch.Tensor):
 
 def _window_t(Wm: torch.Tensor, rows: int, small: int) -> torch.Tensor:
     """Master (rows, 8*small) [r][j][s] -> the overlap-add operand (4*small, 2*rows): row j*small + s,
-    K = [previous time step: tap j+4 | current time step: tap j] (the ConvTranspose1d form of csrc/demucs.hip)."""
+    K = [previous time step: tap j+4 | current time step: tap j] (the ConvTranspose1d form of csrc/demucs.hip's header)."""
     W3 = Wm[:rows].view(rows, 8, small)
     prev = W3[:, 4:8, :].permute(1, 2, 0)
     cur = W3[:, 0:4, :].permute(1, 2, 0)

@@ -7,7 +7,7 @@ instantiated by train.py and are not built.  `forward` gives the loss VALUES (va
 `value_and_grad` also returns the gradient with respect to the predicted waveform (the Demucs backward pass that would consume it is
 not built).
 
-How: a resolution's STFT is one strided-window GEMM on the fp32 matrix cores (csrc/loss.hip, csrc/demucs.hip):
+How: a resolution's STFT is one strided-window GEMM on the fp32 matrix cores (csrc/loss.hip, csrc/demucs_gemm.hip):
 frames x windowed-DFT matrix, K = the window length (600 / 1200 / 240 of the 1024 / 2048 / 512-point frames).
 """
 from __future__ import annotations

@@ -3,7 +3,7 @@
 
 Same constructor defaults, module tree and state_dict keys (encoder.N.0/2, decoder.N.0/2, lstm.lstm.*), same
 ``forward((B, T) or (B, 1, T)) -> (B, 1, T)``, ``valid_length`` and ``total_stride``.  The torch layers are parameter
-containers; forward runs the gfx950 kernels of csrc/demucs.hip (fp32 MFMA GEMMs over time-major activations).
+containers; forward runs the gfx950 kernels of csrc/demucs.hip and csrc/demucs_gemm.hip (MFMA GEMMs over time-major activations).
 The module has no train/eval-dependent layer, so `forward` is the same in both modes; the training STEP (loss, backward,
 Adam -- training/train.py:275-312) is `ops_demucs_train.DemucsTrainEngine`, driven by `training.train.Trainer(input_type=
 "audio")`, not torch autograd.  DemucsStreamer is not built.

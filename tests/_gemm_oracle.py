@@ -1,4 +1,4 @@
-"""Host oracle of mfpa_gemm_mfma (csrc/demucs.hip): a float64 restatement of the formula in include/mfpa.h, an arithmetic model of the
+"""Host oracle of mfpa_gemm_mfma (csrc/demucs_gemm.hip): a float64 restatement of the formula in include/mfpa.h, an arithmetic model of the
 bf16x3 kernels, the error bounds of tests/test_gpu_gemm.py and the case table both the CPU and the GPU tests walk.  No GPU here.
 
     C[b][m][n] = epi( sum_k A[b*strideA + m*lda + k] * W[n*K + k] + bias[n] ),  m < M

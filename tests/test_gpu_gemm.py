@@ -1,4 +1,4 @@
-"""GPU: every kernel behind mfpa_gemm_mfma (csrc/demucs.hip) and every switch of their shared epilogue, element by element, at the
+"""GPU: every kernel behind mfpa_gemm_mfma (csrc/demucs_gemm.hip) and every switch of their shared epilogue, element by element, at the
 tile edges -- against the float64 reference and the bf16x3 arithmetic model of tests/_gemm_oracle.py, with the derived bounds
 stated there (none of them measured).  Outputs are pre-filled with a NaN sentinel whose bit pattern must survive everywhere the
 kernel has no business writing; the gaps between the clips of A hold NaN, which a correct kernel never lets reach an output.

@@ -984,6 +984,48 @@ int mfpa_clip_quantile(const float* x, int B, int T, const float* pct, const uin
 int mfpa_clip_quantile_flat(const float* x, int B, int T, const float* pct, const uint8_t* apply, int n_apply, float* y,
                             void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Resampling by any rational ratio: torchaudio.transforms.Resample(orig_freq, new_freq) (sinc_interp_hann, lowpass_filter_width 6,
+ * rolloff 0.99) as the reference applies it at afp/audfprint/peak_extractor.py:378-388, afp/dejavu/dejavu.py:91-115,
+ * testing/generate_queries.py:39, training/background_noise.py:300 and training/generate_audios.py:51.  torchaudio is NOT in the
+ * reference tree: the filter is restated from its public source, parity with torchaudio itself is unpinned.
+ *   g = gcd(orig, new), o = orig / g, n = new / g, base = min(o, n) * rolloff, width = ceil(lowpass_filter_width * o / base),
+ *   ntaps = 2 * width + o taps for each of the n phases, xpad[m] = x[m - width] inside the clip and 0 outside:
+ *   y[j * n + i] = sum_{k < ntaps} tap[i][k] * xpad[j * o + k], of which the first Tout = ceil(n * T / o) samples are kept.
+ * Limits (MFPA_EINVAL beyond them): n <= MFPA_RESAMPLE_MAX_PHASES, ntaps <= MFPA_RESAMPLE_MAX_TAPS, T <= MFPA_RESAMPLE_MAX_SAMPLES
+ * per clip, B <= 65535, at most MFPA_RESAMPLE_MAX_TILES workgroups per clip.
+ */
+#define MFPA_RESAMPLE_MAX_PHASES 1024
+#define MFPA_RESAMPLE_MAX_TAPS 8192
+#define MFPA_RESAMPLE_MAX_SAMPLES (1LL << 40)
+#define MFPA_RESAMPLE_MAX_TILES (1LL << 23)
+#define MFPA_RESAMPLE_MAX_WINDOW 36864    /* input floats a workgroup stages in LDS, at most */
+#define MFPA_RESAMPLE_TAP_ALIGN 16       /* floats: the taps of a phase start at a multiple of this (a 64-byte line) */
+#define MFPA_RESAMPLE_TAP_PITCH(ntaps) (((ntaps) + MFPA_RESAMPLE_TAP_ALIGN - 1) / MFPA_RESAMPLE_TAP_ALIGN * MFPA_RESAMPLE_TAP_ALIGN)
+/* HOST function, integer and double arithmetic only: the geometry above for T input samples per clip; every output pointer may
+ * be NULL.  MFPA_EINVAL: a rate, lowpass_filter_width or rolloff that is not positive, rolloff > 1, T < 0, or beyond the limits. */
+int mfpa_resample_geometry(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, long long T, int* o, int* n,
+                           int* width, int* ntaps, long long* Tout);
+/* HOST function: frames j one workgroup of mfpa_resample owns for this geometry (tile * n output samples), > 0, or MFPA_EINVAL:
+ * 64 per wave of frames (the 4 or 16 waves of a workgroup split the phases first, then the frames), up to eight such rounds while
+ * one batch of staging loads brings the window, and never more than the window limit admits. */
+int mfpa_resample_tile(int o, int n, int width);
+/* HOST function, float64 math rounded once to float32 (like mfpa_stft_tables): the n * ntaps taps, PHASE-MAJOR with a row pitch of
+ * MFPA_RESAMPLE_TAP_PITCH(ntaps) floats: taps[i * pitch + k] is tap k of phase i, the floats between ntaps and the pitch are
+ * written as 0 and never read (a wave of the kernel works on a few phases and reads their taps with scalar loads of eight, which
+ * want the taps of one phase contiguous and no load across two 64-byte lines).  `taps` holds n * pitch floats.  For phase i, tap k:
+ *   t = ((double)((float)(-i) / (float)n) + (double)(k - width) / o) * base, clamped to +-lowpass_filter_width;
+ *   tap = sinc(pi t) * cos(t pi / lowpass_filter_width / 2)^2 * (base / o). */
+int mfpa_resample_taps(int o, int n, int width, int lowpass_filter_width, double rolloff, float* taps);
+/* x (B, T) float32 with row pitch ldx >= T -> y (B, Tout) float32 with row pitch ldy >= Tout, one launch for the batch;
+ * taps: device copy of mfpa_resample_taps(o, n, width, ...), n * MFPA_RESAMPLE_TAP_PITCH(ntaps) floats (64-byte aligned for
+ * speed; any float alignment is correct).  Every output sample is one fused multiply-add chain over
+ * k = 0 .. ntaps-1: its value depends on its clip's T samples and (o, n, width, taps) only -- not on B, the pitches, the
+ * workgroup it falls in or the memory behind the clip.  B == 0 or Tout == 0: MFPA_OK, no launch.  MFPA_EINVAL before any launch
+ * for null pointers, ldx < T, ldy < Tout, Tout > n * (T / o + 1) and beyond the limits above. */
+int mfpa_resample(const float* x, int B, long long T, long long ldx, int o, int n, int width, const float* taps, float* y,
+                  long long Tout, long long ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,11 @@ _SIGNATURES = {
     "mfpa_pack_conv_weights_batch": ([c_void_p, c_int, c_longlong, c_void_p], c_int),
     "mfpa_adam_step": ([c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float, c_float, c_float, c_int,
                         c_float, c_void_p], c_int),
+    "mfpa_resample_geometry": ([c_int, c_int, c_int, c_double, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "mfpa_resample_tile": ([c_int, c_int, c_int], c_int),
+    "mfpa_resample_taps": ([c_int, c_int, c_int, c_int, c_double, c_void_p], c_int),
+    "mfpa_resample": ([c_void_p, c_int, c_longlong, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_longlong, c_longlong,
+                       c_void_p], c_int),
 }
 
 

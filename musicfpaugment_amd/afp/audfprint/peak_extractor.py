@@ -149,8 +149,9 @@ class Audfprint_peaks(object):
     # ------------------------------------------------------------------ file-level entry points of the reference
     @staticmethod
     def _read_waveform(filename: str, target_sr: int) -> torch.Tensor:
-        """.pkl: the pickled 8 kHz waveform of the reference's query sets (peak_extractor.py:361-368); .wav: PCM / float at the
-        target rate.  mp3 decoding and resampling (torchaudio) are file I/O outside the hot path."""
+        """.pkl: the pickled 8 kHz waveform of the reference's query sets (peak_extractor.py:361-368); .wav: PCM / float at any
+        rate, resampled to `target_sr` on the device like the reference's torchaudio Resample (:378-388; transforms.Resample).
+        mp3 decoding is file I/O outside the hot path."""
         ext = filename.rsplit(".", 1)[-1].lower()
         if ext == "pkl":
             import pickle
@@ -159,11 +160,13 @@ class Audfprint_peaks(object):
         if ext == "wav":
             from scipy.io import wavfile
             sr, data = wavfile.read(filename)
-            if int(sr) != int(target_sr):
-                raise NotImplementedError(f"{filename}: {sr} Hz, expected {target_sr} Hz -- resample offline")
             x = np.asarray(data)
             x = x.astype(np.float32) / float(2 ** (8 * x.dtype.itemsize - 1)) if x.dtype.kind == "i" else x.astype(np.float32)
-            return torch.from_numpy(np.ascontiguousarray(x.mean(axis=1) if x.ndim == 2 else x, dtype=np.float32))
+            d = torch.from_numpy(np.ascontiguousarray(x.mean(axis=1) if x.ndim == 2 else x, dtype=np.float32))
+            if int(sr) != int(target_sr):
+                from ...transforms import Resample
+                d = Resample(int(sr), int(target_sr))(d)
+            return d
         raise NotImplementedError(f"{filename}: only .pkl and .wav inputs (decode other formats offline)")
 
     def wavfile2peaks(self, filename: str, shifts: Optional[int] = None, get_masks_waveforms: bool = False):

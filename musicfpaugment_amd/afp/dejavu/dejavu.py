@@ -36,7 +36,8 @@ def unique_hash(file_path: str, block_size: int = 2 ** 20) -> str:
 
 
 def read(filename: str, denoising: bool = False, denoising_model: str = "unet", *, demucs=None, device="cuda"):
-    """dejavu.py:69-118 for .pkl and .wav at 8 kHz: ([samples x 32767], samplerate, unique_hash).  With denoising_model
+    """dejavu.py:69-118 for .pkl at 8 kHz and .wav at any rate (resampled to 8 kHz on the device like the reference's torchaudio
+    Resample, :91-115): ([samples x 32767], samplerate, unique_hash).  With denoising_model
     "demucs" the waveform goes through `demucs` first (:95-103); the UNet acts later, inside fingerprint()."""
     from ..audfprint.peak_extractor import Audfprint_peaks
     if denoising is True:

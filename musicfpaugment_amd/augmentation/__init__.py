@@ -7,8 +7,9 @@ HighPass -> PeakNormalization, each Bernoulli-gated per example), same `__call__
 Differences, on purpose:
   * impulse responses and background noises live in banks resident in HBM, given in memory (`ir_bank`, `noise_bank`;
     `synthetic_banks()` builds deterministic ones) or read ONCE at construction from the reference's arguments
-    (`impulse_response_dir`, `background_paths`) when they hold PCM / float .wav files already at `sample_rate` -- the
-    reference decodes and resamples a file per example with torchaudio (file I/O is out of scope, SURVEY.md §2);
+    (`impulse_response_dir`, `background_paths`) when they hold PCM / float .wav files, already at `sample_rate` or, with
+    `resample_banks=True`, resampled once on the device -- the reference decodes and resamples a file per example (decoding
+    other codecs is file I/O and out of scope, SURVEY.md §2);
   * the random draws use the same distributions (torch.distributions / random.choice) but are made for the whole batch
     on the host; the per-sample arithmetic runs in csrc/augment.hip;
   * by default `batch_augment` treats every example like `__call__` does, which is how the training data is made
@@ -66,14 +67,15 @@ def _find_wavs(paths: List[str]) -> List[str]:
     return out
 
 
-def _read_wav(path: str, sample_rate: int) -> torch.Tensor:
+def _read_wav(path: str, sample_rate: int, resample: bool = False) -> torch.Tensor:
     """A PCM / float .wav as a mono float32 tensor in [-1, 1] (the reference decodes with torchaudio and resamples on the fly,
-    augmentation/utils.py:140-330; here the file must already be at `sample_rate`: resampling and other codecs are file I/O,
-    outside the hot path)."""
+    augmentation/utils.py:140-330).  A file at another rate is refused unless `resample`: then it is resampled on the device
+    (transforms.Resample).  Other codecs are file I/O, outside the hot path."""
     from scipy.io import wavfile
     sr, data = wavfile.read(path)
-    if int(sr) != int(sample_rate):
-        raise NotImplementedError(f"{path}: {sr} Hz, expected {sample_rate} Hz -- resample the banks offline")
+    if int(sr) != int(sample_rate) and not resample:
+        raise NotImplementedError(f"{path}: {sr} Hz, expected {sample_rate} Hz -- resample the banks offline or pass "
+                                  "resample_banks=True")
     x = np.asarray(data)
     if x.dtype.kind == "i":
         x = x.astype(np.float32) / float(2 ** (8 * x.dtype.itemsize - 1))
@@ -83,7 +85,11 @@ def _read_wav(path: str, sample_rate: int) -> torch.Tensor:
         x = x.astype(np.float32)
     if x.ndim == 2:
         x = x.mean(axis=1)                                               # mono=True
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    if int(sr) != int(sample_rate):
+        from ..transforms import Resample
+        x = Resample(int(sr), int(sample_rate))(x)
+    return x
 
 
 def synthetic_banks(seed: int = 0, sample_rate: int = 8000, n_ir: int = 8, n_noise: int = 8, noise_seconds: float = 10.0):
@@ -141,19 +147,23 @@ class AugmentFP(object):
     def __init__(self, background_paths: Optional[Dict[str, List[str]]] = None, sample_rate: int = 8000,
                  parameters: Dict[str, float] = DEFAULT_PARAMETERS, impulse_response_dir: Optional[str] = None, *,
                  ir_bank: Optional[List[torch.Tensor]] = None, noise_bank: Optional[Dict[str, List[torch.Tensor]]] = None,
-                 device="cuda", clipping_scope: str = "example") -> None:
+                 device="cuda", clipping_scope: str = "example", resample_banks: bool = False) -> None:
+        """`resample_banks`: impulse-response and noise files at another rate than `sample_rate` are resampled once, at
+        construction, on the device (default: such a file is refused).  The reference resamples its banks with
+        librosa.core.resample; this is the torchaudio-style windowed-sinc filter of transforms.Resample instead, so parity
+        with librosa is not claimed."""
         if clipping_scope not in ("example", "batch"):
             raise ValueError("clipping_scope must be 'example' (like __call__) or 'batch' (the reference's batch_augment)")
         self.clipping_scope = clipping_scope
         if ir_bank is None:
             if impulse_response_dir is None:
                 raise ValueError("pass `impulse_response_dir` (a directory of .wav files) or an in-memory `ir_bank`")
-            ir_bank = [_read_wav(os.path.join(impulse_response_dir, f), int(sample_rate))
+            ir_bank = [_read_wav(os.path.join(impulse_response_dir, f), int(sample_rate), resample_banks)
                        for f in sorted(os.listdir(impulse_response_dir)) if f.endswith(".wav")]      # __init__.py:41-45
         if noise_bank is None:
             if background_paths is None:
                 raise ValueError("pass `background_paths` ({scene: [files or directories]}) or an in-memory `noise_bank`")
-            noise_bank = {scene: [_read_wav(f, int(sample_rate)) for f in _find_wavs(paths)]
+            noise_bank = {scene: [_read_wav(f, int(sample_rate), resample_banks) for f in _find_wavs(paths)]
                           for scene, paths in background_paths.items()}
             noise_bank = {k: v for k, v in noise_bank.items() if len(v) > 0}
         if len(ir_bank) == 0 or len(noise_bank) == 0:

@@ -149,6 +149,74 @@ def f64_to_f32(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------- resampling (csrc/resample.hip)
+RESAMPLE_LOWPASS_FILTER_WIDTH = 6      # torchaudio.transforms.Resample's defaults (sinc_interp_hann); torchaudio is not in the
+RESAMPLE_ROLLOFF = 0.99                # reference tree, so parity with it is unpinned
+RESAMPLE_TAP_ALIGN = 16                # MFPA_RESAMPLE_TAP_ALIGN
+
+
+def resample_geometry(orig_freq: int, new_freq: int, T: int = 0) -> Tuple[int, int, int, int, int]:
+    """(o, n, width, taps per phase, Tout) of torchaudio.transforms.Resample(orig_freq, new_freq) for T input samples
+    (mfpa_resample_geometry: host arithmetic)."""
+    o, n, width, ntaps = (ctypes.c_int(0) for _ in range(4))
+    tout = ctypes.c_longlong(0)
+    check(lib().mfpa_resample_geometry(int(orig_freq), int(new_freq), RESAMPLE_LOWPASS_FILTER_WIDTH, RESAMPLE_ROLLOFF, int(T),
+                                       ctypes.addressof(o), ctypes.addressof(n), ctypes.addressof(width), ctypes.addressof(ntaps),
+                                       ctypes.addressof(tout)), "mfpa_resample_geometry")
+    return o.value, n.value, width.value, ntaps.value, int(tout.value)
+
+
+def resample_tile(orig_freq: int, new_freq: int) -> int:
+    """Frames (groups of n output / o input samples) one workgroup of the resampling kernel owns for this pair of rates."""
+    o, n, width, _, _ = resample_geometry(orig_freq, new_freq)
+    tile = lib().mfpa_resample_tile(o, n, width)
+    check(min(tile, 0), "mfpa_resample_tile")
+    return tile
+
+
+@lru_cache(maxsize=32)
+def _resample_taps_cached(o: int, n: int, device_index: int) -> torch.Tensor:
+    _, _, width, ntaps, _ = resample_geometry(o, n)
+    taps = np.empty((n, resample_tap_pitch(ntaps)), dtype=np.float32)
+    check(lib().mfpa_resample_taps(o, n, width, RESAMPLE_LOWPASS_FILTER_WIDTH, RESAMPLE_ROLLOFF,
+                                   taps.ctypes.data_as(ctypes.c_void_p)), "mfpa_resample_taps")
+    return torch.from_numpy(taps).to(torch.device("cuda", device_index))
+
+
+def resample_tap_pitch(ntaps: int) -> int:
+    """MFPA_RESAMPLE_TAP_PITCH: floats from the taps of one phase to the next in the bank."""
+    return (ntaps + RESAMPLE_TAP_ALIGN - 1) // RESAMPLE_TAP_ALIGN * RESAMPLE_TAP_ALIGN
+
+
+def resample_taps(orig_freq: int, new_freq: int, device) -> torch.Tensor:
+    """The filter bank of the pair of rates, phase-major (n, resample_tap_pitch(taps per phase)) float32 on `device`, zero behind
+    the taps of each row (mfpa_resample_taps: built on the host in float64, uploaded once per (o, n, device))."""
+    o, n, _, _, _ = resample_geometry(orig_freq, new_freq)
+    device = torch.device(device)
+    return _resample_taps_cached(o, n, device.index if device.index is not None else torch.cuda.current_device())
+
+
+def resample(wav: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:
+    """torchaudio.transforms.Resample(orig_freq, new_freq) of (B, T) float32 on the GPU -> (B, ceil(T * new / orig)).  Equal rates
+    return `wav` itself, like torchaudio."""
+    require_gpu(wav, "waveform")
+    if wav.dim() != 2 or wav.dtype != torch.float32:
+        raise ValueError("waveform must be (B, T) float32")
+    if int(orig_freq) <= 0 or int(new_freq) <= 0:
+        raise ValueError("Original frequency and desired frequecy should be positive")       # torchaudio's own message
+    if int(orig_freq) == int(new_freq):
+        return wav
+    wav = wav.contiguous()
+    B, T = wav.shape
+    o, n, width, _, Tout = resample_geometry(orig_freq, new_freq, T)
+    out = torch.empty((B, Tout), dtype=torch.float32, device=wav.device)
+    if B == 0 or Tout == 0:
+        return out
+    taps = resample_taps(orig_freq, new_freq, wav.device)
+    check(lib().mfpa_resample(ptr(wav), B, T, T, o, n, width, ptr(taps), ptr(out), Tout, Tout, stream()), "mfpa_resample")
+    return out
+
+
 # ----------------------------------------------------------------------------- Audfprint picker
 # testing/parameters.py:17-26 (afp_settings["audfprint"])
 AUDFPRINT_DENSITY = 20

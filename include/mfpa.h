@@ -1026,6 +1026,50 @@ int mfpa_resample_taps(int o, int n, int width, int lowpass_filter_width, double
 int mfpa_resample(const float* x, int B, long long T, long long ldx, int o, int n, int width, const float* taps, float* y,
                   long long Tout, long long ldy, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Training segments out of whole tracks: the chunk / drop-silence / draw / normalise stage of the reference's AugmentationDataset
+ * (training/dataset.py:55-122) and the crops of testing/generate_queries.py:43-49.  Tracks sit back to back in one device float32
+ * buffer `bank`: track i owns bank[off[i] .. off[i] + len[i]) (off, len: int64; any 4-byte alignment of a track is fine).
+ * With frame length L and step S (tf.signal.frame, no end padding) track i has nf[i] = 1 + (len[i] - L) / S segments, 0 when
+ * len[i] < L; segment j of track i starts at off[i] + j * S and has the GLOBAL index seg_off[i] + j, seg_off being the exclusive
+ * prefix of nf (n_tracks + 1 ints, NS = seg_off[n_tracks] segments in all).
+ * Limits (MFPA_EINVAL beyond them): 1 <= L, S <= MFPA_SEGMENT_MAX_LENGTH, nf[i] <= MFPA_SEGMENT_MAX_PER_TRACK (the sort keys of a
+ * track live in LDS), NS <= INT_MAX, n_tracks * n_keep <= INT_MAX, rows <= INT_MAX.
+ */
+#define MFPA_SEGMENT_MAX_PER_TRACK 8192
+#define MFPA_SEGMENT_MAX_LENGTH (1LL << 27)
+/* HOST function, integers only: seg_off[0 .. n_tracks] from the HOST array len.  MFPA_EINVAL: a null pointer (len may be NULL when
+ * n_tracks == 0), n_tracks < 0, a negative length, or beyond the limits above. */
+int mfpa_segment_geometry(const long long* len, int n_tracks, long long L, long long S, int* seg_off);
+/* off, len, seg_off: DEVICE copies.  seg_sumsq[NS] (double): sum of x^2 over each segment; trk_sumsq[n_tracks] (double): over each
+ * whole track, the tail no segment covers included; trk_peak[n_tracks] (float): max|x| of each whole track (exact).  Every square
+ * is taken in float64 (exact for a float32 sample) and added with one rounding, in an order fixed by the sample's position in its
+ * segment (or in the tail) alone: no floating-point atomics, and each output is bit for bit the same whatever other tracks are in
+ * the call and wherever the track lies in `bank`.  S == L: the audio is read once, a track's sum is its segments' sums plus its
+ * tail's in a fixed order; otherwise the track is read a second time for its own sum.  Empty tracks give 0 / 0 / 0.
+ * n_tracks == 0: MFPA_OK, no launch.  MFPA_EINVAL before any launch for null pointers and beyond the limits. */
+int mfpa_segment_stats(const float* bank, const long long* off, const long long* len, const int* seg_off, int n_tracks, long long L,
+                       long long S, double* seg_sumsq, double* trk_sumsq, float* trk_peak, void* stream);
+/* One workgroup per track.  Segment j of track i is KEPT iff, in float64,
+ *   seg_sumsq[j] * (double)len[i] > (thr * trk_sumsq[i]) * (double)L        (thr = exp(dbs_threshold / 5), thr >= 0)
+ * which is the reference's 10 * ln(rms_seg / rms_track) > dbs_threshold (dataset.py:86-99) without the square roots and the
+ * logarithm; an all-zero track keeps nothing.  kept[i] = segments kept, before the cut to n_keep; mask[NS] (uint8, may be NULL) =
+ * the keep flags.  The winners are the kept segments in ascending (keys[j], j) order, keys being NS uint32 the host drew before it
+ * knew the mask: shuffle(kept)[:n_keep] (dataset.py:104-122) with no host round trip.  Row r = i * n_keep + k, k < n_keep:
+ *   sel[r] = global index of the k-th winner, src[r] = its first sample in `bank` (int64), both -1 when kept[i] <= k;
+ *   div[r] = trk_peak[i] when do_norm and the peak is > 0, else 1 (dataset.py:55-60).
+ * n_tracks == 0: MFPA_OK, no launch.  MFPA_EINVAL before any launch for null pointers (mask excepted), n_keep < 1, thr < 0 or NaN
+ * and beyond the limits. */
+int mfpa_segment_select(const double* seg_sumsq, const double* trk_sumsq, const float* trk_peak, const long long* off, const long long* len,
+                        const int* seg_off, int n_tracks, long long L, long long S, const unsigned int* keys, double thr, int n_keep,
+                        int do_norm, int* sel, long long* src, float* div, int* kept, unsigned char* mask, void* stream);
+/* out[r * ldo + t] = bank[src[r] + t] / div[r] for t < L, an IEEE float32 division (a plain copy when div == NULL); rows with
+ * src[r] < 0 are left untouched, and so are the floats between L and ldo.  src[r] may have any alignment; the caller guarantees
+ * that src[r] + L stays inside `bank`.  rows == 0: MFPA_OK, no launch.  MFPA_EINVAL before any launch for null pointers (div
+ * excepted), ldo < L and beyond the limits. */
+int mfpa_segment_gather(const float* bank, const long long* src, const float* div, long long rows, long long L, float* out, long long ldo,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1070,6 +1070,41 @@ int mfpa_segment_select(const double* seg_sumsq, const double* trk_sumsq, const 
 int mfpa_segment_gather(const float* bank, const long long* src, const float* div, long long rows, long long L, float* out, long long ldo,
                         void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Composable waveform transforms (augmentation/transformations/band_filters.py, colored_noise.py): what the AugmentFP kernels
+ * above do not already cover.  Gain, Clipping, PeakNormalization, ApplyImpulseResponse, AddBackgroundNoise and the pass filters
+ * are the entry points of the AugmentFP section; AddColoredNoise mixes with mfpa_mix_background.
+ */
+/* Band-pass taps, julius 0.2.7 BandPassFilter restated (julius is NOT in the reference tree: parity unpinned, like
+ * mfpa_lowpass_taps): two windowed-sinc low-passes at cut_lo[b] < cut_hi[b] (fractions of the sample rate, 0 < c <= 0.5) on ONE
+ * window of 2*half[b]+1 points, half = int(8 / cut_lo / 2), each normalised to its own unit sum in the arithmetic of
+ * mfpa_lowpass_taps (but the sine is taken of the phase c * (k - half) reduced to half a turn, exactly, which a window of tens of
+ * thousands of points needs to keep the taps within 2e-7 of their float64 values); taps[tap_off[b] + k] = hi[k] - lo[k].  One pass of mfpa_fir (pad_mode 0, off = half) is then the band-pass
+ * (out_mode 0) or the band-stop x - bandpass (out_mode 1).  B == 0: MFPA_OK, no launch. */
+int mfpa_bandpass_taps(const float* cut_lo, const float* cut_hi, const int* half, const long long* tap_off, int B, float* taps,
+                       void* stream);
+/* The real FFT of the library: N real samples as N/2 complex points in one LDS buffer of a workgroup, Stockham passes of
+ * radix 5, 3, 4 and 2.  The buffer is 64 KiB -- 8 bytes per complex point -- so N/2 <= 8192: MFPA_RFFT_MAX_N.  (The kernel's whole
+ * LDS need is that buffer plus 64 bytes of reduction scratch.) */
+#define MFPA_RFFT_MAX_N 16384
+#define MFPA_RFFT_MAX_RADICES 16
+/* HOST function, integers only: which N the device FFT takes and how.  MFPA_OK when N is even, 4 <= N <= MFPA_RFFT_MAX_N and
+ * N/2 = 2^a 3^b 5^c: radices[0 .. *n_radices) are the passes in order (their product is N/2; `radices` holds
+ * MFPA_RFFT_MAX_RADICES ints, the rest are written as 0), *lds_bytes the LDS bytes of the workgroup.  Every output pointer may
+ * be NULL.  MFPA_EINVAL for every other N -- an odd N on purpose: torch's irfft of an rfft of N odd samples returns N-1. */
+int mfpa_rfft_plan(int N, int* radices, int* n_radices, int* lds_bytes);
+/* HOST function, float64 math rounded once to float32 (like mfpa_stft_tables): out[2q], out[2q+1] = cos, -sin of 2 pi q / N for
+ * q < N (2N floats).  MFPA_EINVAL: a null pointer or an N mfpa_rfft_plan refuses. */
+int mfpa_rfft_twiddles(int N, float* out);
+/* AddColoredNoise._gen_noise (colored_noise.py:12-38) for B examples, one workgroup each:
+ *   white (B, N) float32 -> rfft -> * 1 / linspace(1, sqrt(N/2), N/2+1)^f_decay[b] (float32, torch.linspace's two-sided form)
+ *   -> irfft (scaled by 1/N) -> x / (sqrt(mean(x^2)) + 1e-8) -> out[b, t] = x[t mod N], t < T    (out (B, T) float32, T >= 1).
+ * twiddles: device copy of mfpa_rfft_twiddles(N), 8-byte aligned.  Every value of `out` depends on its example's N samples,
+ * f_decay[b] and N only: fixed summation orders, no atomics -- bit for bit independent of B, of the row and of T.
+ * MFPA_EINVAL before any launch: a null pointer, B < 0, T < 1, an N mfpa_rfft_plan refuses.  B == 0: MFPA_OK, no launch. */
+int mfpa_colored_noise(const float* white, int B, int N, const float* f_decay, int T, const float* twiddles, float* out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

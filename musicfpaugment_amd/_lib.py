@@ -206,6 +206,10 @@ _SIGNATURES = {
     "mfpa_segment_select": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_longlong, c_void_p,
                              c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_segment_gather": ([c_void_p, c_void_p, c_void_p, c_longlong, c_longlong, c_void_p, c_longlong, c_void_p], c_int),
+    "mfpa_bandpass_taps": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
+    "mfpa_rfft_plan": ([c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "mfpa_rfft_twiddles": ([c_int, c_void_p], c_int),
+    "mfpa_colored_noise": ([c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
 }
 
 

@@ -170,6 +170,32 @@ def g13_dejavu_denoised(fp, versions):
     save("g13_dejavu_denoised", amp_min_low=AMP_MIN_LOW, seeds=np.array(seeds), shape=np.array(mask.shape), versions=versions, **out)
 
 
+G19_RATES = (600, 1000, 8000)
+G19_DECAYS = (-2.0, 0.0, 1.0, 2.0)
+
+
+def g19_colored_noise(versions):
+    """G19: the REAL _gen_noise (augmentation/transformations/colored_noise.py:12-38) on the CPU.  Per sample rate one white-noise
+    draw (seed 1900 + rate: the generator is seeded, torch.normal(0, 1, (rate,)) recorded, the generator seeded again, _gen_noise
+    called -- so it draws the same samples), four decays, and two lengths: rate + 7 (longer than one period, not a multiple of it)
+    and rate // 2 + 3 (shorter than one period)."""
+    import torch
+    from augmentation.transformations.colored_noise import _gen_noise
+
+    out = {}
+    for sr in G19_RATES:
+        seed = 1900 + sr
+        torch.manual_seed(seed)
+        out[f"white_{sr}"] = torch.normal(0.0, 1.0, (sr,)).numpy()
+        for i, fd in enumerate(G19_DECAYS):
+            for T in (sr + 7, sr // 2 + 3):
+                torch.manual_seed(seed)
+                y = _gen_noise(torch.tensor(fd, dtype=torch.float32), T, "cpu", sr)      # a 0-d tensor, as apply_transform passes it
+                assert y.shape == (T,) and y.dtype == torch.float32
+                out[f"noise_{sr}_{i}_{T}"] = y.numpy()
+    save("g19_colored_noise", rates=np.array(G19_RATES), f_decay=np.array(G19_DECAYS, dtype=np.float32), versions=versions, **out)
+
+
 def main():
     import scipy.signal
     import torch
@@ -187,6 +213,9 @@ def main():
         return
     if "--only-g13" in sys.argv:
         g13_dejavu_denoised(fp, versions)
+        return
+    if "--only-g19" in sys.argv:
+        g19_colored_noise(versions)
         return
 
     # ---- G1 / G2: spectrogram() and audfprint stft on two 1-second clips -------------------
@@ -448,6 +477,7 @@ def main():
          mag0_sub=m0[0, ::7, ::9].copy(), mag0_shape=np.array(m0.shape), sc_silent=float(zs), mag_silent=float(zm), versions=versions)
     g12_demucs_train_step(versions)
     g13_dejavu_denoised(fp, versions)
+    g19_colored_noise(versions)
     print("done")
 
 

@@ -1105,6 +1105,38 @@ int mfpa_rfft_twiddles(int N, float* out);
 int mfpa_colored_noise(const float* white, int B, int N, const float* f_decay, int T, const float* twiddles, float* out,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Complex STFT and its inverse (csrc/stft.hip, csrc/istft.hip): the library's fixed geometry (n_fft 512, hop 256, one-sided 257
+ * bins, centre / reflect framing), float64 arithmetic, the window of `tables` (mfpa_stft_tables).  Additive to ABI 47.
+ *
+ * mfpa_stft_complex: torch.stft(x.double(), 512, 256, window=w, return_complex=True).
+ *   wav      (B, T_w) float32, T_w > 256 (the rules of mfpa_stft_mag; B == 0: MFPA_OK, no launch)
+ *   spec     (B, 257, n_frames) complex128 as interleaved (re, im) doubles, 16-byte aligned
+ *   mag      may be NULL; otherwise (B, 257, n_frames) of mag_dtype, bit for bit what mfpa_stft_mag writes for the same input
+ *   clip_max may be NULL; otherwise (B) float64, bit for bit mfpa_stft_mag's */
+int mfpa_stft_complex(const float* wav, int B, int T_w, const double* tables, double* spec, void* mag, int mag_dtype,
+                      double* clip_max, void* stream);
+/* mfpa_istft: torch.istft(Z, 512, 256, window=w, center=True, length=length) -- per frame the inverse real FFT (the imaginary parts
+ * of bins 0 and 256 are ignored, as torch's c2r transform ignores them) times the window, overlap-added, divided by the
+ * overlap-added squared window, first 256 samples dropped.
+ *   spec   (B, 257, n_frames) complex128 as interleaved doubles, 16-byte aligned
+ *   mag    NULL: Z = spec.  Otherwise (B, 257, n_frames) of mag_dtype and Z = m * spec / |spec| with m = mag * denom[b]
+ *          (denom (B) float64, may be NULL: m = mag); where |spec| == 0, Z = m (phase 0).  With MFPA_ISTFT_CLAMP in `flags` a
+ *          negative m becomes 0; without it a negative m flips the sign.  Z is formed as the spectrum is read and never stored.
+ *   out    (B, length) of out_dtype; the float32 output is the float64 value rounded once
+ * Every output sample is the sum of at most two frames, added in frame order, by one thread: no atomics, and a row of `out` is
+ * bit for bit independent of B, of the row's position and of the memory around its operands.
+ * MFPA_EINVAL before any launch: a null spec / tables / out, n_frames < 2, length outside
+ * [256 (n_frames - 1), 256 n_frames) -- the lengths an STFT with that many frames can have come from --, an unknown dtype or flag
+ * bit, a spec that is not 16-byte aligned, B < 0 or B > 65535.  B == 0: MFPA_OK, no launch. */
+#define MFPA_ISTFT_CLAMP 1
+int mfpa_istft(const double* spec, const void* mag, int mag_dtype, const double* denom, int flags, int B, int n_frames, int length,
+               const double* tables, void* out, int out_dtype, void* stream);
+/* HOST function, no GPU work: *out_min = the minimum over the kept samples [256, 256 + length) of the overlap-added squared
+ * window, float64, summed in frame order like mfpa_istft's divisor (torch.istft refuses a minimum below 1e-11: "window overlap
+ * add min").  MFPA_EINVAL: a null pointer, or n_frames / length outside mfpa_istft's rules. */
+int mfpa_istft_envelope_min(const double* window512, int n_frames, int length, double* out_min);
+
 #ifdef __cplusplus
 }
 #endif

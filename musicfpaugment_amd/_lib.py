@@ -210,6 +210,9 @@ _SIGNATURES = {
     "mfpa_rfft_plan": ([c_int, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_rfft_twiddles": ([c_int, c_void_p], c_int),
     "mfpa_colored_noise": ([c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "mfpa_stft_complex": ([c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
+    "mfpa_istft": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p], c_int),
+    "mfpa_istft_envelope_min": ([c_void_p, c_int, c_int, c_void_p], c_int),
 }
 
 

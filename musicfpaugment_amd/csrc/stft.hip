@@ -11,54 +11,26 @@
 // Magnitudes are staged in LDS as [bin][16 frames] so the global store writes 16-frame
 // segments of each bin row.  All arithmetic is float64 (the reference's window is float64,
 // which promotes the whole STFT): HBM traffic is 514 KB per 8 s clip, the FFT ~4 MFLOP.
-#include "mfpa_common.h"
+// mfpa_stft_complex is the same kernel with SPEC set: the complex bins leave through a second, complex LDS tile before the
+// magnitudes do (+1.03 MB per 8 s clip); csrc/istft.hip runs the transform backwards.  The butterflies are in mfpa_fft16.h.
+#include "mfpa_fft16.h"
 
 #include <cmath>
 
 namespace {
 
-struct cd {
-  double re, im;
-};
-__device__ __forceinline__ cd operator+(cd a, cd b) { return {a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ cd operator-(cd a, cd b) { return {a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ cd cmul(cd a, cd b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-
-__device__ __forceinline__ void dft4(cd& a, cd& b, cd& c, cd& d) {
-  cd s0 = a + c, s1 = a - c, s2 = b + d, s3 = b - d;
-  a = s0 + s2;
-  c = s0 - s2;
-  b = {s1.re + s3.im, s1.im - s3.re};  // s1 - i s3
-  d = {s1.re - s3.im, s1.im + s3.re};  // s1 + i s3
-}
-
-// In-place 16-point DFT.  On return X[k] sits at v[4*(k&3) + (k>>2)].
-__device__ __forceinline__ void dft16(cd (&v)[16]) {
-  constexpr double C1 = 0.92387953251128673848, S1 = 0.38268343236508978178, R2 = 0.70710678118654752440;
-#pragma unroll
-  for (int j2 = 0; j2 < 4; ++j2) dft4(v[j2], v[4 + j2], v[8 + j2], v[12 + j2]);
-  // v[4*k1 + j2] *= W16^(j2*k1)
-  v[4 * 1 + 1] = cmul(v[4 * 1 + 1], cd{C1, -S1});
-  v[4 * 1 + 2] = cmul(v[4 * 1 + 2], cd{R2, -R2});
-  v[4 * 1 + 3] = cmul(v[4 * 1 + 3], cd{S1, -C1});
-  v[4 * 2 + 1] = cmul(v[4 * 2 + 1], cd{R2, -R2});
-  v[4 * 2 + 2] = cd{v[4 * 2 + 2].im, -v[4 * 2 + 2].re};  // * -i
-  v[4 * 2 + 3] = cmul(v[4 * 2 + 3], cd{-R2, -R2});
-  v[4 * 3 + 1] = cmul(v[4 * 3 + 1], cd{S1, -C1});
-  v[4 * 3 + 2] = cmul(v[4 * 3 + 2], cd{-R2, -R2});
-  v[4 * 3 + 3] = cmul(v[4 * 3 + 3], cd{-C1, S1});
-#pragma unroll
-  for (int k1 = 0; k1 < 4; ++k1) dft4(v[4 * k1], v[4 * k1 + 1], v[4 * k1 + 2], v[4 * k1 + 3]);
-}
-
 constexpr int FRAMES_PER_BLOCK = 16;
-constexpr int SLOTS = 16 * 17;  // padded 16x16 tile of doubles per frame (>= 257 + 1 slots of the [bin][16 frames] output tile per frame)
+constexpr int SLOTS = FFT16_SLOTS;  // padded 16x16 tile of doubles per frame (>= 257 + 1 slots of the [bin][16 frames] output tile per frame)
 
 // MODE 0: centre/reflect magnitude (hypot).  MODE 1: no padding, one-sided PSD (|X|^2, interior bins x2).
-template <int MODE, typename OutT>
-__global__ __launch_bounds__(256, 4) void stft_kernel(const float* __restrict__ wav, int T_w, int nF,
-                                                   const double* __restrict__ tables, OutT* __restrict__ out,
-                                                   double* __restrict__ clip_max, double scale_in) {
+// SPEC (MODE 0 only): the complex bins go to `spec` as well, through a [bin][16 frames] tile of complex values that takes the whole
+// SPEC_TILE_BYTES of LDS (two resident workgroups per CU); `out` and `clip_max` may then be null, and what they receive is what the
+// SPEC = false kernel writes: the magnitudes are the same expressions of the same values.
+template <int MODE, typename OutT, bool SPEC = false>
+__global__ __launch_bounds__(256, SPEC ? 2 : 4) void stft_kernel(const float* __restrict__ wav, int T_w, int nF,
+                                                              const double* __restrict__ tables, OutT* __restrict__ out,
+                                                              double* __restrict__ clip_max, double scale_in,
+                                                              double2* __restrict__ spec) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* buf = reinterpret_cast<double*>(smem);
   const int tid = threadIdx.x, l = tid & 15, fs = tid >> 4;
@@ -103,15 +75,10 @@ __global__ __launch_bounds__(256, 4) void stft_kernel(const float* __restrict__ 
     }
   }
   dft16(a);  // A[k1] at a[4*(k1&3) + (k1>>2)]
-  // The 16 lanes of a frame sit in ONE wavefront (4 frames per wave), so the two exchanges need no workgroup barrier: a wave's LDS
-  // operations execute in order, wave_sync() only keeps the compiler from moving them across each other.  Real and imaginary parts
-  // go through the same 8-byte slots one after the other: 34 KB of LDS per workgroup instead of 68 KB -- four resident
-  // workgroups per CU instead of two (the kernel is latency-bound: profiles/r03_prune_sq.md, 1.8 waves per SIMD, 38 % issuing).
-  auto wave_sync = [] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
+  // The exchange of mfpa_fft16.h's fft256_lanes(), spelled out: called through that function's array references this kernel came out
+  // with 8 spilled registers under its 128-VGPR bound.  Real and imaginary parts go through the same 8-byte slots one after the
+  // other: 34 KB of LDS per workgroup instead of 68 KB -- four resident workgroups per CU instead of two (the kernel is
+  // latency-bound: profiles/r03_prune_sq.md, 1.8 waves per SIMD, 38 % issuing).
   cd c[16];
   {
     double tim[16];
@@ -160,6 +127,7 @@ __global__ __launch_bounds__(256, 4) void stft_kernel(const float* __restrict__ 
     zni[m] = mybuf[kn + (kn >> 4)];
   }
   double lo[9], hi[9];
+  cd sk[9], sn[9];   // SPEC: bins k and 256-k
 #pragma unroll
   for (int m = 0; m < 9; ++m) {
     const int k = (m < 8) ? l + 16 * m : 128;
@@ -168,7 +136,11 @@ __global__ __launch_bounds__(256, 4) void stft_kernel(const float* __restrict__ 
     const cd o = {0.5 * (zk.im + zn.im), -0.5 * (zk.re - zn.re)};  // -i (zk - conj(zn)) / 2
     const double2 t = *reinterpret_cast<const double2*>(tw512 + 2 * k);
     const cd wo = cmul(cd{t.x, t.y}, o);
-    const cd xk = e + wo, xn = e - wo;
+    const cd xk = e + wo, xn = e - wo;   // X[k] and conj(X[256-k])
+    if (SPEC) {
+      sk[m] = xk;
+      sn[m] = {xn.re, -xn.im};
+    }
     if (MODE == 0) {
       lo[m] = hypot(xk.re, xk.im);          // (sqrt(fma(re, re, im * im)) measured the same time and the same bits on the synthetic clips: kept hypot, numpy's abs)
       hi[m] = hypot(xn.re, xn.im);
@@ -178,6 +150,25 @@ __global__ __launch_bounds__(256, 4) void stft_kernel(const float* __restrict__ 
     }
   }
   __syncthreads();
+  if (SPEC) {
+    const int nvalid = min(FRAMES_PER_BLOCK, nF - f0);
+    double2* ctile = reinterpret_cast<double2*>(smem);  // [257][SPEC_TILE_PITCH]
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const int k = l + 16 * m;
+      ctile[k * SPEC_TILE_PITCH + fs] = double2{sk[m].re, sk[m].im};
+      ctile[(256 - k) * SPEC_TILE_PITCH + fs] = double2{sn[m].re, sn[m].im};   // k == 0: the Nyquist bin
+    }
+    if (l == 0) ctile[128 * SPEC_TILE_PITCH + fs] = double2{sk[8].re, sk[8].im};
+    __syncthreads();
+    double2* sbase = spec + (size_t)b * MFPA_N_BINS * nF + f0;
+    for (int idx = tid; idx < MFPA_N_BINS * FRAMES_PER_BLOCK; idx += 256) {
+      const int bin = idx >> 4, fr = idx & 15;
+      if (fr < nvalid) sbase[(size_t)bin * nF + fr] = ctile[bin * SPEC_TILE_PITCH + fr];
+    }
+    if (out == nullptr && clip_max == nullptr) return;   // the same for every thread of the grid
+    __syncthreads();
+  }
   double* tile = reinterpret_cast<double*>(smem);  // [257][16]
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
@@ -197,7 +188,7 @@ __global__ __launch_bounds__(256, 4) void stft_kernel(const float* __restrict__ 
     if (fr < nvalid) {
       const double v = tile[idx];
       vmax = fmax(vmax, v);
-      obase[(size_t)bin * nF + fr] = (OutT)v;
+      if (!SPEC || out != nullptr) obase[(size_t)bin * nF + fr] = (OutT)v;
     }
   }
   if (clip_max != nullptr) {
@@ -272,9 +263,28 @@ int mfpa_stft_mag(const float* wav, int B, int T_w, const double* tables, void* 
   dim3 grid((nF + FRAMES_PER_BLOCK - 1) / FRAMES_PER_BLOCK, B);
   const size_t lds = sizeof(double) * SLOTS * FRAMES_PER_BLOCK;
   if (out_dtype == MFPA_F64)
-    hipLaunchKernelGGL((stft_kernel<0, double>), grid, dim3(256), lds, s, wav, T_w, nF, tables, (double*)mag, clip_max, 1.0);
+    hipLaunchKernelGGL((stft_kernel<0, double>), grid, dim3(256), lds, s, wav, T_w, nF, tables, (double*)mag, clip_max, 1.0, nullptr);
   else
-    hipLaunchKernelGGL((stft_kernel<0, float>), grid, dim3(256), lds, s, wav, T_w, nF, tables, (float*)mag, clip_max, 1.0);
+    hipLaunchKernelGGL((stft_kernel<0, float>), grid, dim3(256), lds, s, wav, T_w, nF, tables, (float*)mag, clip_max, 1.0, nullptr);
+  MFPA_CHECK_LAUNCH();
+  return MFPA_OK;
+}
+
+int mfpa_stft_complex(const float* wav, int B, int T_w, const double* tables, double* spec, void* mag, int mag_dtype,
+                      double* clip_max, void* stream) {
+  if (B == 0) return MFPA_OK;
+  if (!wav || !tables || !spec || B < 0 || T_w <= 256) return MFPA_EINVAL;
+  if (mag_dtype != MFPA_F32 && mag_dtype != MFPA_F64) return MFPA_EINVAL;
+  if (reinterpret_cast<uintptr_t>(spec) & 15) return MFPA_EINVAL;
+  hipStream_t s = mfpa_stream(stream);
+  const int nF = mfpa_stft_frames(T_w);
+  if (clip_max) MFPA_HIP(hipMemsetAsync(clip_max, 0, sizeof(double) * B, s));
+  dim3 grid((nF + FRAMES_PER_BLOCK - 1) / FRAMES_PER_BLOCK, B);
+  double2* sp = reinterpret_cast<double2*>(spec);
+  if (mag_dtype == MFPA_F64)
+    hipLaunchKernelGGL((stft_kernel<0, double, true>), grid, dim3(256), SPEC_TILE_BYTES, s, wav, T_w, nF, tables, (double*)mag, clip_max, 1.0, sp);
+  else
+    hipLaunchKernelGGL((stft_kernel<0, float, true>), grid, dim3(256), SPEC_TILE_BYTES, s, wav, T_w, nF, tables, (float*)mag, clip_max, 1.0, sp);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
 }
@@ -290,7 +300,7 @@ int mfpa_specgram_psd(const float* wav, int B, int T_w, double scale_in, const d
   if (clip_max) MFPA_HIP(hipMemsetAsync(clip_max, 0, sizeof(double) * B, s));
   dim3 grid((nF + FRAMES_PER_BLOCK - 1) / FRAMES_PER_BLOCK, B);
   const size_t lds = sizeof(double) * SLOTS * FRAMES_PER_BLOCK;
-  hipLaunchKernelGGL((stft_kernel<1, double>), grid, dim3(256), lds, s, wav, T_w, nF, tables, psd, clip_max, scale_in);
+  hipLaunchKernelGGL((stft_kernel<1, double>), grid, dim3(256), lds, s, wav, T_w, nF, tables, psd, clip_max, scale_in, nullptr);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
 }

@@ -18,6 +18,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
+from .. import ops
 from .. import ops_unet as K
 from .._lib import MfpaError, require_gpu
 
@@ -237,3 +238,14 @@ class UNet(nn.Module):
             for s, e in ranges:
                 outs.append(K.unet_forward_eval(pw, spec64=spec64[s:e], denom=clip_max[s:e].contiguous()))
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+    def denoise_waveform(self, wav: torch.Tensor, per_clip: bool = False, clamp: bool = True) -> torch.Tensor:
+        """(B, T) float32 mixture -> (B, T) float32 denoised audio, the call shape Demucs has: one complex STFT, denoise_spectrogram on
+        its magnitudes, and the inverse STFT of the denoised magnitudes (times the denominator the normalisation divided by) on the
+        mixture's phase.  clamp=True zeroes the negative magnitudes the last layer can emit (it has no ReLU)."""
+        if self.training:
+            raise MfpaError("denoise_waveform is the inference path; call .eval()")
+        spec, mag, clip_max = ops.stft_complex(wav, want_mag=True)
+        den = self.denoise_spectrogram(mag, clip_max, per_clip)
+        denom = clip_max if per_clip else clip_max.max().expand(wav.shape[0]).contiguous()
+        return ops.istft(spec, wav.shape[1], mag=den, denom=denom, clamp=clamp)

@@ -2,7 +2,7 @@
 // templates, twelve instantiations, one shared epilogue, one route (gemm_route) and one launch table (GEMM_KERNELS) -- and the two fused
 // end-level kernels (glu_convT_c1_kernel, c1_glu_kernel), which are the short-K bf16x3 GEMM with another loader and epilogue.
 // Written once at the top of the file: the tile geometry of every kernel shape (read by the kernel and by its launch), the bf16 hi | lo
-// split, the bf16x3 product, the accumulator clear, the fragment pointer and the bf16x3 wave step.  A piece stays written out in a kernel
+// split, the accumulator clear, the fragment pointer and the bf16x3 wave step.  A piece stays written out in a kernel
 // where the shared spelling changes that kernel's instruction stream (hipcc simplifies a helper on its own before it inlines it); those
 // places say so, and tools/same_kernels.py is the check.
 #include "mfpa_common.h"
@@ -11,7 +11,7 @@
 
 namespace {
 
-using namespace mfpa_tile;     // vector types, pin_reads ("one MFMA, then k LDS reads", LEFT reads spread over SLOTS MFMAs)
+using namespace mfpa_tile;     // vector types, the bf16x3 product mfma_bf16x3, pin_reads ("one MFMA, then k LDS reads", LEFT reads spread over SLOTS MFMAs)
 
 struct GemmArgs {
   const float* A; long long lda, strideA;      // A[b][m][k] = A[b*strideA + m*lda + k]
@@ -87,13 +87,6 @@ __device__ __forceinline__ void split_store(char* row, int q, int lo_off, f32x4 
   }
   *reinterpret_cast<bf16x4*>(row + 8 * q) = hi;
   *reinterpret_cast<bf16x4*>(row + lo_off + 8 * q) = lo;
-}
-
-// the bf16x3 product: lo.hi, hi.lo, hi.hi (small terms first; the order is part of the arithmetic model of tests/_gemm_oracle.py)
-__device__ __forceinline__ void mfma_bf16x3(floatx16& acc, bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
 }
 
 template <int NT>
@@ -539,7 +532,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_wide_kernel(GemmArgs a) {
   for (int mt = 0; mt < 2; ++mt) gemm_epilogue(a, acc[mt], m0, n0 + wn * 64, b, wm * 2 + mt, li, lh);
 }
 
-// The software-pipelined form of the wide kernel (the schedule of conv_mfma_kernel<PREC 1>'s tap body, unet.hip): 8 waves own a
+// The software-pipelined form of the wide kernel (the schedule of conv_mfma_kernel<PREC 1>'s tap body, unet_mfma.hip): 8 waves own a
 // 256 x 128 tile (4 x 2 waves of 64 x 64), one workgroup per CU.  A K chunk of 32 is two k-steps; the fragments of a k-step are
 // read from LDS one step AHEAD of the MFMAs that use them (two register sets of fragments), the barrier sits between the two
 // k-steps of a chunk, and the global loads run two chunks ahead of their LDS stores through two register sets (straight-line

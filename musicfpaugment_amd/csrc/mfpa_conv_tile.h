@@ -1,4 +1,5 @@
-// What the MFMA convolution sources share: the vector types (csrc/unet.hip, unet_wd16.hip, unet_ws.hip, unet_up.hip), the "one MFMA, then k LDS reads"
+// What the MFMA convolution sources share: the vector types (csrc/unet.hip, unet_mfma.hip, unet_wd16.hip, unet_ws.hip, unet_up.hip), the chunk width KC,
+// the DPP row-shift add of the fused reductions (unet_mfma.hip, unet_wd16.hip), the "one MFMA, then k LDS reads"
 // scheduling pattern (also csrc/demucs_gemm.hip, with the vector types; csrc/lstm.hip and csrc/demucs_train.hip take the types too), the bf16 hi | lo split of the bf16x3 products, a compile-time index loop, and -- namespace
 // mfpa_tile::role_split -- the tile geometry and LDS plane layout of the two role-split kernels (conv_ws64_kernel, conv_up_kernel).
 #pragma once
@@ -16,6 +17,13 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+constexpr int KC = 32;        // channels per K chunk of every convolution kernel of the UNet family (and of the routing's divisibility rules)
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_row_add(float v) {               // v + (v of the lane CTRL names; 0 where there is none)
+  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
 
 // sched_group_barrier pattern "one MFMA, then k LDS reads" with LEFT reads spread evenly over SLOTS MFMAs
 template <int SLOTS, int LEFT, int I = 0>
@@ -44,6 +52,15 @@ __device__ __forceinline__ void split_bf16x3(f32x2 x, unsigned& hi, unsigned& lo
   lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
 }
 
+// the bf16x3 product of one tile: lo.hi, hi.lo, hi.hi (small terms first; the order is part of the arithmetic model of tests/_gemm_oracle.py and of
+// the exact-operand tests).  csrc/demucs_gemm.hip's seven bf16x3 kernels and convT_mfma_kernel (csrc/unet_mfma.hip); conv_mfma_kernel runs the same
+// three terms over all of a wave's tiles each (its mfma_terms).
+__device__ __forceinline__ void mfma_bf16x3(floatx16& acc, bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+}
+
 // f(integral_constant<int, FIRST>{}, a...), ..., f(integral_constant<int, FIRST + N - 1>{}, a...): straight-line code, the index a compile-time
 // constant
 template <int FIRST, class F, int... I, class... A>
@@ -58,7 +75,6 @@ __device__ __forceinline__ void each_index(F&& f, A&&... a) {
 // conv_ws64_kernel (csrc/unet_ws.hip) and conv_up_kernel (csrc/unet_up.hip): 8 x 32 output tiles, 4 compute + 4 loader waves, two LDS stages
 // of eight planes [hi | lo][k-group] of (halo pixel x 16 B), a 64 KB output tile for the loaders to store
 namespace role_split {
-constexpr int KC = 32;                                                 // channels per K chunk
 constexpr int PH = 8, PW = 32, HPW = PW + 2, HPH = PH + 2, HP = HPW * HPH;   // the halo patch: 10 x 34
 constexpr int THREADS = 512, LTHREADS = 256;
 constexpr int SPP = KC / 4;                                            // staging slots (16 B = 4 fp32 channels) per pixel and chunk

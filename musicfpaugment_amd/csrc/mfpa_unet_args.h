@@ -1,5 +1,5 @@
-// Kernel-side argument block of the UNet convolution kernels (csrc/unet.hip, csrc/unet_wd16.hip, csrc/unet_ws.hip); filled from mfpa_conv_desc
-// (include/mfpa.h) by mfpa_conv_mfma and the other entry points of unet.hip.  Below it: what unet.hip's routing needs from the kernels' own files.
+// Kernel-side argument block of the UNet convolution kernels (csrc/unet_mfma.hip, csrc/unet_wd16.hip, csrc/unet_ws.hip); filled from mfpa_conv_desc
+// (include/mfpa.h) by mfpa_conv_mfma and the other entry points of csrc/unet.hip.  Below it: what unet.hip's routing needs from the kernels' own files.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,5 +92,22 @@ __attribute__((visibility("hidden"))) int launch_wd16(ConvArgs& a, hipStream_t s
 // channels up, and the tile (wmw, bn, ph, pw) of a (W, Cout)
 __attribute__((visibility("hidden"))) extern const int CONV_WD16_ROWS;
 __attribute__((visibility("hidden"))) void conv_wd16_tile(int W, int Cout, mfpa_conv_route* t);
+
+// csrc/unet_mfma.hip: the row-image kernels.  conv_mfma_kernel<BN, PH, PW, WM, WN, MODE, PREC, C1SRC> (the fp32 chain's 3x3 convolution, the
+// C1SRC fallback, MODE 2 = the transposed convolution's input gradient; WM x WN = PH * PW / 64 x BN / 64 waves, derived in its geometry) and
+// convT_mfma_kernel<PH, PW, PREC, IO16, PLAIN> (the transposed convolution's forward), every instantiation written ONCE as above.
+#define MFPA_MFMA_FORMS(X) /* <BN, PH, PW, MODE, PREC, C1SRC> */                                                                      \
+  X(64, 8, 32, 0, 0, 0) X(128, 8, 32, 0, 0, 0) X(128, 4, 32, 0, 0, 0) X(64, 4, 32, 0, 0, 0) X(128, 8, 16, 0, 0, 0) X(64, 8, 16, 0, 0, 0) \
+  X(64, 8, 32, 0, 1, 0) X(128, 8, 32, 0, 1, 0) X(128, 4, 32, 0, 1, 0) X(64, 4, 32, 0, 1, 0) X(128, 8, 16, 0, 1, 0) X(64, 8, 16, 0, 1, 0) \
+  X(64, 8, 32, 2, 0, 0) X(128, 8, 32, 2, 0, 0) X(128, 4, 32, 2, 0, 0) X(64, 4, 32, 2, 0, 0) X(128, 8, 16, 2, 0, 0) X(64, 8, 16, 2, 0, 0) \
+  X(64, 8, 32, 2, 1, 0) X(128, 8, 32, 2, 1, 0) X(128, 4, 32, 2, 1, 0) X(64, 4, 32, 2, 1, 0) X(128, 8, 16, 2, 1, 0) X(64, 8, 16, 2, 1, 0) \
+  X(128, 16, 16, 0, 1, 0) X(64, 8, 32, 0, 0, 1) X(64, 8, 32, 0, 1, 1)
+#define MFPA_CONVT_FORMS(X) /* <PH, PW, PREC, IO16, PLAIN> */                                                                          \
+  X(4, 32, 0, 0, 0) X(4, 32, 1, 0, 0) X(4, 32, 1, 1, 0) X(4, 32, 1, 1, 1) X(8, 16, 0, 0, 0) X(8, 16, 1, 0, 0) X(8, 16, 1, 1, 0) X(8, 16, 1, 1, 1)
+// size LDS and the grid from the kernel's geometry and launch that instantiation; reject nothing.  Return MFPA_OK / a HIP error code.
+template <int BN, int PH, int PW, int MODE, int PREC, bool C1SRC>
+__attribute__((visibility("hidden"))) int launch_conv(ConvArgs& a, hipStream_t s);
+template <int PH, int PW, int PREC, bool IO16, bool PLAIN>
+__attribute__((visibility("hidden"))) int launch_convT(ConvArgs& a, hipStream_t s);
 
 }  // namespace mfpa_unet

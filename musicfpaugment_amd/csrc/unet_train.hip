@@ -1,6 +1,6 @@
 // Training-step kernels of the UNet denoiser for MI355X (gfx950): the pieces of
 // Trainer.train_epoch's spec branch (training/train.py:257-317 of the reference) that are not the
-// convolution itself (csrc/unet.hip) or its weight gradient (csrc/unet_wgrad.hip):
+// convolution itself (csrc/unet.hip and the kernels' own files) or its weight gradient (csrc/unet_wgrad.hip):
 //
 //   BatchNorm batch statistics + running-stat update, BN/ReLU/max-pool forward glue,
 //   BN/ReLU backward (reduce + apply), max-pool backward,
@@ -677,7 +677,7 @@ inline int grid_for(long long work, int per_block = 256, int cap = 256 * 16) {
 }
 
 // Convolution weights [tap][Co][Ci] (the master fp32 layout) -> the operand image a conv launch reads: precision 0: [tap][row n][K]
-// floats; precision 1: the bf16x3 image of csrc/unet.hip, [tap][chunk of 32 k][row n][128 B = 32 bf16 hi | 32 bf16 lo in 16-byte
+// floats; precision 1: the bf16x3 image of csrc/unet_mfma.hip, [tap][chunk of 32 k][row n][128 B = 32 bf16 hi | 32 bf16 lo in 16-byte
 // slots XOR-swizzled by the row] (what ops_unet.split_bf16x3 builds on the host).  TR = false: n = co in [row0, row0 + nrows), k = ci (forward).  TR = true: the input-gradient operand --
 // tap t reads source tap taps-1-t when taps == 9 (the 3x3 kernel flipped; the 2x2 transposed conv keeps its tap), n = ci in
 // [row0, row0 + nrows), k = co.  One workgroup per 32 x 32 (n, k) tile and tap, transposed through LDS so both sides coalesce.
@@ -711,7 +711,7 @@ __device__ __forceinline__ void pack_conv_weights_tile(float (*tile)[33], const 
       ob[at] = hi;
       ob[at + 512] = lo;
     } else {
-      // the bf16x3 image of csrc/unet.hip: [tap][chunk][row][8 slots of 16 B], logical slot (hi: 0-3, lo: 4-7) at physical slot ^ swz(row)
+      // the bf16x3 image of csrc/unet_mfma.hip: [tap][chunk][row][8 slots of 16 B], logical slot (hi: 0-3, lo: 4-7) at physical slot ^ swz(row)
       const int row = n0 + r, swz = (row >> 1) & 7;
       __bf16* ob = reinterpret_cast<__bf16*>(out + (((size_t)t * (K / 32) + k0 / 32) * nrows + row) * 32);
       const __bf16 hi = (__bf16)v;

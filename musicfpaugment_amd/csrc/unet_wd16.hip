@@ -7,10 +7,8 @@
 
 namespace {
 
-using namespace mfpa_tile;     // vector types, pin_reads / pin_read_slots, each_index
+using namespace mfpa_tile;     // vector types, KC, dpp_row_add, pin_reads / pin_read_slots, each_index
 using mfpa_unet::ConvArgs;
-
-constexpr int KC = 32;        // channels per K chunk
 
 // ---- The kernel's LDS layout and its persistence rule, said once for the kernel and its launcher.  Dynamic LDS of a workgroup, in this order:
 //   two halo stages (STAGE bytes each: eight planes [hi | lo][k-group 0..3] of HPS pixels x 16 B)
@@ -62,11 +60,6 @@ static_assert(Wd16Lds<8, 32, false>::fixed_bytes(4) == 124672 && Wd16Lds<8, 32, 
 //   image: [tap][chunk = Cin / 32][Cout / 16][hi | lo][lane 64][16 B], lane (g = l >> 4, c = l & 15) = channel 16 t + c, k 32 chunk + 8 g .. + 7
 //          (ops_unet.split_bf16x3_frag(w, 2), mfpa_pack_conv_weights(precision 3)).
 // Not bit-identical to the 32 x 32 x 16 kernels (a k-step sums 32 products inside the instruction); same products, fp32 accumulate.
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_row_add(float v) {               // v + (v of the lane CTRL names; 0 where there is none)
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
 
 template <int PH, int PW, bool ROWS, int WMW = 2, bool SIDE = false, bool PLAIN = false, bool IN16 = false, bool AFF16 = false>
 __global__ __launch_bounds__(512, 1) void conv_wd16_kernel(ConvArgs a) {

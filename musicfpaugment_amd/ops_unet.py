@@ -1,4 +1,4 @@
-"""UNet building blocks over the C ABI (csrc/unet.hip and the kernels' own files unet_wd16.hip, unet_ws.hip, unet_up.hip): weight packing and the eval forward.
+"""UNet building blocks over the C ABI (csrc/unet.hip and the kernels' own files unet_mfma.hip, unet_wd16.hip, unet_ws.hip, unet_up.hip): weight packing and the eval forward.
 
 Activations are NHWC float32 tensors (B, H, W, C) -- H = frequency bins, W = frames.
 """
@@ -37,7 +37,7 @@ def pack_convT2x2(w: torch.Tensor) -> torch.Tensor:
 
 
 def split_bf16x3(w: torch.Tensor) -> torch.Tensor:
-    """Kernel-layout fp32 weights [taps][Cout][Cin] -> the bf16x3 operand image of the convolution kernels (csrc/unet.hip, PREC 1):
+    """Kernel-layout fp32 weights [taps][Cout][Cin] -> the bf16x3 operand image of the convolution kernels (csrc/unet_mfma.hip, PREC 1):
     [tap][chunk = Cin / 32][Cout][128 bytes], a row = the 32 channels of a chunk split w = hi + lo (+ O(2^-17 w)) into 8 slots
     of 16 bytes, logical slots 0-3 = 32 bf16 hi, 4-7 = 32 bf16 lo, stored at physical slot (logical ^ ((row >> 1) & 7)) -- a
     (tap, chunk, 128-row) tile is 16 KB contiguous and goes into LDS verbatim by LDS-DMA, the XOR keeps the fragment reads

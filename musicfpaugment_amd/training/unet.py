@@ -3,7 +3,7 @@
 Same constructor, same module tree (hence the same 118 state_dict keys: published
 checkpoints ``{"model_state_dict": ...}`` load unchanged), same ``forward((B,1,F,T)) ->
 (B,1,F,T)`` contract.  The torch ``nn`` layers below are parameter containers only: forward
-never calls them.  It runs the hand-written gfx950 kernels of libmfpa.so (csrc/unet.hip):
+never calls them.  It runs the hand-written gfx950 kernels of libmfpa.so (csrc/unet.hip and the kernels' own files, csrc/unet_*.hip):
 NHWC activations, float32 MFMA implicit-GEMM convolutions with the eval-mode BatchNorm
 folded into a per-channel affine + ReLU epilogue, pad + concat folded into the decoder
 convolutions' loaders.  There is no PyTorch/CPU fallback.

@@ -80,7 +80,7 @@ def relative_l1(y: torch.Tensor, ref: torch.Tensor) -> float:
 
 
 def forward_bf16x3_model(x: torch.Tensor, sd: Dict[str, torch.Tensor]) -> torch.Tensor:
-    """Arithmetic MODEL of the device's bf16x3 convolutions (csrc/unet.hip, PREC 1) on the CPU, eval mode: every fp32 operand of
+    """Arithmetic MODEL of the device's bf16x3 convolutions (csrc/unet_mfma.hip, PREC 1) on the CPU, eval mode: every fp32 operand of
     the MFMA layers is split x = hi + lo into two bfloat16 values and a product is hi*hi + hi*lo + lo*hi (the lo*lo term is
     dropped), accumulated wide; the 1-channel first layer and the 1x1 OutConv stay fp32 (they run on the vector ALUs).  Test
     infrastructure: lets the CPU suite bound the error of the headline arithmetic on any weight family before a GPU is involved

@@ -18,7 +18,8 @@ WD16_FORMS_WMW2 = [(0, 0, 0, 0, 0), (0, 1, 0, 0, 0), (1, 0, 0, 0, 0), (1, 1, 0, 
                    (1, 1, 1, 0, 0), (1, 0, 1, 1, 0), (1, 1, 1, 1, 0), (1, 1, 1, 1, 1)]
 WD16_FORMS_WMW4 = [(0, 0, 0, 0, 0), (0, 1, 0, 0, 0), (0, 0, 1, 0, 0), (0, 1, 1, 0, 0), (0, 0, 1, 1, 0), (0, 1, 1, 1, 0), (0, 1, 1, 1, 1)]
 
-# every instantiation the launcher's table (CONV_KERNELS, csrc/unet.hip; the 29 wd16 forms from MFPA_WD16_FORMS, csrc/mfpa_unet_args.h) names:
+# every instantiation the launcher's table (CONV_KERNELS, csrc/unet.hip; the 29 wd16, 27 mfma and 8 convT forms from MFPA_WD16_FORMS / MFPA_MFMA_FORMS / MFPA_CONVT_FORMS,
+# csrc/mfpa_unet_args.h; the row-image kernels themselves: csrc/unet_mfma.hip) names:
 # 2 + 29 + 27 + 8 = 66 kernels
 KERNELS = (
     {("ws64", 0), ("ws64", 1)}

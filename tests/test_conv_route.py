@@ -1,6 +1,6 @@
 """mfpa_conv_mfma_route (include/mfpa.h): the routing of the UNet convolution family, host arithmetic only -- no GPU.  The case table
 (tests/_conv_route_cases.py) pins which template instantiation serves a descriptor, the threshold edges pin each constant of the "Tile
-choice" block of csrc/unet.hip, the rejects pin that the route and the launcher refuse the same descriptors, and the query sweep pins
+choice" block of csrc/unet.hip (the row-image kernels it names live in csrc/unet_mfma.hip), the rejects pin that the route and the launcher refuse the same descriptors, and the query sweep pins
 that mfpa_conv_scale_folds / mfpa_conv_c1_layout / mfpa_conv_stats_rows say what the route says."""
 import ctypes
 import os

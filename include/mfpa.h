@@ -1137,6 +1137,34 @@ int mfpa_istft(const double* spec, const void* mag, int mag_dtype, const double*
  * add min").  MFPA_EINVAL: a null pointer, or n_frames / length outside mfpa_istft's rules. */
 int mfpa_istft_envelope_min(const double* window512, int n_frames, int length, double* out_min);
 
+/* ---------------------------------------------------------------------------------------
+ * Phase vocoder (csrc/vocoder.hip): torchaudio.functional.phase_vocoder at the library's fixed geometry (257 bins, hop 256) with
+ * one rate PER CLIP, float64 throughout.  The arithmetic is restated from torchaudio's public source (torchaudio is not in the
+ * reference tree: parity with it is unpinned, as for mfpa_resample).  Additive to ABI 47.
+ *
+ * Clip b, rate r = rates[b], n_out = ceil(n_frames / r) in double (the length of torch.arange(0, n_frames, r)); output frame
+ * i < n_out of bin k:
+ *   t = i * r, j = floor(t), alpha = t - j;  Z0 = spec[b, k, j], Z1 = spec[b, k, j + 1] (0 past the last frame)
+ *   d = angle(Z1) - angle(Z0) - adv_k, adv_k = pi k (torch.linspace(0, pi * 256, 257)[k]);  d -=2 pi round(d / 2 pi);  inc_i = d + adv_k
+ *   phi_i = angle(spec[b, k, 0]) + sum_{m < i} inc_m
+ *   out[b, k, i] = (alpha |Z1| + (1 - alpha) |Z0|) * (cos phi_i, sin phi_i)
+ * Frames n_out <= i < ld_out are written as zeros.  A clip whose rate is exactly 1.0 is copied through (torchaudio's rule).
+ *   spec   (B, 257, n_frames) complex128 as interleaved doubles, 16-byte aligned
+ *   rates  (B) float64 on the device
+ *   out    (B, 257, ld_out) complex128, 16-byte aligned
+ *   n_out  (B) int32 on the device: the clip's frame count, or -1 for a rate the kernel refuses -- not finite, not positive, or
+ *          with n_out > ld_out; such a clip's output is all zeros.  The rates live on the device, so the host cannot check them.
+ * One wavefront owns one row (b, k) and scans it in 64-frame chunks with a carry: a fixed summation order, no atomics; a row's
+ * bits do not depend on B, on the row's position or on its neighbours.
+ * MFPA_EINVAL before any launch: B < 0 or B > 65535, n_frames < 1, ld_out < 1, n_frames or ld_out > MFPA_VOCODER_MAX_FRAMES, and
+ * with B > 0 a null or misaligned pointer.  B == 0: MFPA_OK, no launch. */
+#define MFPA_VOCODER_MAX_FRAMES 16384
+int mfpa_phase_vocoder(const double* spec, int B, int n_frames, const double* rates, double* out, int ld_out, int* n_out,
+                       void* stream);
+/* HOST function, no GPU work: *n_out = ceil(n_frames / rate) by the double arithmetic of the kernel.  MFPA_EINVAL: a null pointer,
+ * n_frames < 1 or > MFPA_VOCODER_MAX_FRAMES, a rate that is not finite or not positive, a result above MFPA_VOCODER_MAX_FRAMES. */
+int mfpa_vocoder_frames(int n_frames, double rate, int* n_out);
+
 #ifdef __cplusplus
 }
 #endif

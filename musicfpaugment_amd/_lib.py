@@ -213,6 +213,8 @@ _SIGNATURES = {
     "mfpa_stft_complex": ([c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
     "mfpa_istft": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p], c_int),
     "mfpa_istft_envelope_min": ([c_void_p, c_int, c_int, c_void_p], c_int),
+    "mfpa_phase_vocoder": ([c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
+    "mfpa_vocoder_frames": ([c_int, c_double, c_void_p], c_int),
 }
 
 

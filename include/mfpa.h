@@ -1026,6 +1026,50 @@ int mfpa_resample_taps(int o, int n, int width, int lowpass_filter_width, double
 int mfpa_resample(const float* x, int B, long long T, long long ldx, int o, int n, int width, const float* taps, float* y,
                   long long Tout, long long ldy, void* stream);
 
+/* Sparse-tap form of the same resampler, for the pairs of rates whose dense bank is out of reach (8979 : 8000, two semitones at
+ * 8 kHz, would be 8993 taps for each of 8000 phases).  Additive to ABI 47; the mfpa_resample* functions above keep their limits,
+ * their results and their routing.
+ *
+ * The window argument t of a tap is clamped to +-lowpass_filter_width, and at the clamp cos^2(pi / 2) * sinc * scale is about
+ * 1e-49 in float64, which rounds to 0.0f: only the taps of the run |t| < lowpass_filter_width, at most 2 * width + 1 consecutive
+ * k per phase, are not zero.  The sparse bank keeps support = S = 2 * width + 1 rounded up to a multiple of 4 taps per phase (a
+ * row is a multiple of 16 bytes) from k = first[i] on:
+ *   y[j * n + i] = chain over u = 0 .. S-1 of acc = fmaf(taps[i * S + u], xpad[j * o + first[i] + u], acc), from acc = 0.f
+ * -- ONE ascending chain, the dense chain without its zero taps.  Hence, where mfpa_resample takes the pair, both give the same
+ * float32 value for finite input, with two differences: the SIGN of a zero result may differ (the dense chain adds products with
+ * zero taps, which can turn -0 into +0), and a NaN or Inf input sample spreads over every output whose DENSE window holds it but
+ * here only over the outputs whose support holds it.
+ * Limits (MFPA_EINVAL beyond them, nothing written): n <= MFPA_RESAMPLE_SPARSE_MAX_PHASES (every pair of rates below 65 536 Hz),
+ * o <= MFPA_RESAMPLE_SPARSE_MAX_ORIG, 2 * width + 1 <= MFPA_RESAMPLE_SPARSE_MAX_SUPPORT (width <= 255: a decimation of about
+ * 42 : 1), T <= MFPA_RESAMPLE_MAX_SAMPLES, B <= 65535, at most MFPA_RESAMPLE_MAX_TILES workgroups per clip. */
+#define MFPA_RESAMPLE_SPARSE_MAX_PHASES 65536
+#define MFPA_RESAMPLE_SPARSE_MAX_ORIG (1 << 20)
+#define MFPA_RESAMPLE_SPARSE_MAX_SUPPORT 512
+/* HOST function: o, n, width and Tout as mfpa_resample_geometry gives them, support = S; every output pointer may be NULL. */
+int mfpa_resample_sparse_geometry(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, long long T, int* o, int* n,
+                                  int* width, int* support, long long* Tout);
+/* HOST function: consecutive OUTPUT samples one workgroup of mfpa_resample_sparse owns, > 0, or MFPA_EINVAL: a multiple of 64,
+ * 1024 unless the input span of that many outputs (about tile * o / n + S floats, staged in LDS) would pass 16384 floats.
+ * MFPA_EINVAL also for a width so small for o / n that 64 outputs span more than MFPA_RESAMPLE_MAX_WINDOW floats (never the width
+ * of mfpa_resample_sparse_geometry); mfpa_resample_sparse refuses the same. */
+int mfpa_resample_sparse_tile(int o, int n, int width);
+/* HOST function: taps (n * S floats), first (n ints).  Row i holds taps k = first[i] .. first[i] + S - 1 of row i of the dense
+ * bank, each bit for bit what mfpa_resample_taps writes for (i, k) -- one expression in the source serves both --; positions
+ * with k >= ntaps hold 0.0f (first[i] >= 0).  The builder PROVES that what it leaves out is zero: outside the run
+ * |t| < lowpass_filter_width the clamped argument is exactly -lowpass_filter_width or +lowpass_filter_width, so a dropped tap has
+ * one of two values; both are evaluated and must be 0.0f, the run of every phase (found with the float64 t itself) must fit in S
+ * taps, and first[i] - floor(i * o / n) must lie in [0, 3] (the kernel sizes its LDS window by that; it is 1 or 2 in practice) --
+ * else MFPA_EINVAL with nothing written.  n * S tap evaluations, never n * ntaps. */
+int mfpa_resample_sparse_taps(int o, int n, int width, int lowpass_filter_width, double rolloff, float* taps, int32_t* first);
+/* x (B, T) float32 with row pitch ldx >= T -> y (B, Tout) float32 with row pitch ldy >= Tout, one launch for the batch.
+ * taps, first: device copies of mfpa_resample_sparse_taps(o, n, width, ...), taps 16-byte aligned; support = S of the geometry.
+ * Every output sample is the one chain above: its value depends on its clip's T samples and the table only -- not on B, the
+ * pitches, the workgroup it falls in or the memory behind the clip.  B == 0 or Tout == 0: MFPA_OK, no launch.  MFPA_EINVAL before
+ * any launch for null pointers, a misaligned taps, support != S, ldx < T, ldy < Tout, Tout > n * (T / o + 1) and beyond the
+ * limits above. */
+int mfpa_resample_sparse(const float* x, int B, long long T, long long ldx, int o, int n, int width, int support, const float* taps,
+                         const int32_t* first, float* y, long long Tout, long long ldy, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Training segments out of whole tracks: the chunk / drop-silence / draw / normalise stage of the reference's AugmentationDataset
  * (training/dataset.py:55-122) and the crops of testing/generate_queries.py:43-49.  Tracks sit back to back in one device float32

@@ -200,6 +200,11 @@ _SIGNATURES = {
     "mfpa_resample_taps": ([c_int, c_int, c_int, c_int, c_double, c_void_p], c_int),
     "mfpa_resample": ([c_void_p, c_int, c_longlong, c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_longlong, c_longlong,
                        c_void_p], c_int),
+    "mfpa_resample_sparse_geometry": ([c_int, c_int, c_int, c_double, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "mfpa_resample_sparse_tile": ([c_int, c_int, c_int], c_int),
+    "mfpa_resample_sparse_taps": ([c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p], c_int),
+    "mfpa_resample_sparse": ([c_void_p, c_int, c_longlong, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                              c_longlong, c_longlong, c_void_p], c_int),
     "mfpa_segment_geometry": ([c_void_p, c_int, c_longlong, c_longlong, c_void_p], c_int),
     "mfpa_segment_stats": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p,
                             c_void_p], c_int),

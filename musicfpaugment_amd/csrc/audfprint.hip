@@ -13,11 +13,19 @@
 //             one 64-lane wavefront owns a clip: 4 bins per lane, threshold in registers,
 //             per-frame top-k by wavefront arg-max (value desc, bin desc), columns prefetched
 //             4 frames ahead.  Latency-bound by design; parallelism comes from clips.
+//   pick        : prep_sum_kernel (mfpa_prepsum.h: log values frame-major + the node sums of np.mean's pairwise tree, many
+//                 workgroups per clip) + the pruner filtering the frames itself as it walks them.
+//   pick_track  : the same two launches for whole tracks, up to 16384 frames -- what the 14 time bits of the hash table hold
+//                 without wrapping (afp/audfprint/hash_table.py:55 of the reference; its find_peaks, peak_extractor.py:236-311,
+//                 takes a file of any length).  The pruner's event list and frame table, which bound a clip to 1500 frames in
+//                 LDS, live in a per-track slice of a global workspace; the frame step is the same code, so the peak set equals
+//                 that of pick / prepare + prune bit for bit wherever both apply.
 #include "mfpa_common.h"
 #include "mfpa_fastlog.h"
 #include "mfpa_nplog.h"
 #include "mfpa_npsum.h"
 #include "mfpa_prepsum.h"
+#include <type_traits>
 
 namespace {
 
@@ -245,19 +253,40 @@ __device__ __forceinline__ Best wave_best(Best x) {
 // FUSED: `filtered` holds the LOG values frame-major with pitch R + 1 (prep_sum_kernel, fm = 1) and the kernel applies
 // "minus mean, 1-pole high-pass along the frames" itself while it walks the frames forward (state in registers, exactly prepare's
 // arithmetic) -- the filtered spectrogram never exists in memory.
-template <bool FUSED>
+// GLOBAL_EV (whole tracks, FUSED only): the event list and the frame table live in global memory instead of LDS (which then holds the
+// Gaussian row only): ev / ep [B][T * maxpks], fs [B][T + 2] as int (up to 131072 entries).  Only this wavefront touches its clip's
+// slice.  The backward pass reads what the forward pass wrote behind the workgroup barrier between the passes (which drains the wave's
+// stores), the emission what the backward pass wrote behind the second one; the same-frame read-modify-write of `ep` in the backward
+// pass concerns entries of frames c and c + 1 only, while the loads in flight are those of frame c - 1.  Two more things follow the
+// switch: the node sums lie at the stride the launcher passes (2 * nchunks doubles per clip, up to 514 chunks) instead of 2 * MAX_CHUNKS,
+// and the mask is zeroed by the launcher's memset instead of by this wave.  Without it, sum_stride / ev_all / ep_all / fs_all are unused.
+template <bool FUSED, bool GLOBAL_EV>
 __global__ __launch_bounds__(64) void prune_kernel(const double* __restrict__ filtered, int R, int T,
                                                    const double* __restrict__ gauss, double a_dec, int maxpks,
                                                    uint8_t* __restrict__ mask, int32_t* __restrict__ npeaks,
-                                                   const double* __restrict__ node_sums, const double* __restrict__ denom, double pole) {
+                                                   const double* __restrict__ node_sums, long long sum_stride,
+                                                   const double* __restrict__ denom, double pole,
+                                                   double* ev_all, int* ep_all, int* fs_all) {
+  static_assert(FUSED || !GLOBAL_EV, "the whole-track pruner is the fused one");
+  using FsT = std::conditional_t<GLOBAL_EV, int, short>;       // a frame-table cell
+  constexpr bool ZERO_MASK = FUSED && !GLOBAL_EV;              // the clip's mask is zeroed here, not by a memset in the launcher
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x, b = blockIdx.x;
   const int cap = T * maxpks;                                  // most peaks a clip can record
   double* G = reinterpret_cast<double*>(smem);                 // [2R+2]
-  double* ev = G + (2 * R + 2);                                // [cap] peak values, in recording order (frame, then rank)
-  int* ep = reinterpret_cast<int*>(ev + cap);                  // [cap] frame << 8 | bin; sign bit set = pruned
-  short* fs = reinterpret_cast<short*>(ep + cap);              // [T + 2] first entry of every frame, fs[T] = number of entries
+  double* ev;                                                  // [cap] peak values, in recording order (frame, then rank)
+  int* ep;                                                     // [cap] frame << 8 | bin; sign bit set = pruned
+  FsT* fs;                                                     // [T + 2] first entry of every frame, fs[T] = number of entries
+  if constexpr (GLOBAL_EV) {
+    ev = ev_all + (size_t)b * cap;
+    ep = ep_all + (size_t)b * cap;
+    fs = fs_all + (size_t)b * (T + 2);
+  } else {
+    ev = G + (2 * R + 2);
+    ep = reinterpret_cast<int*>(ev + cap);
+    fs = reinterpret_cast<FsT*>(ep + cap);
+  }
 
-  const int lane = threadIdx.x, b = blockIdx.x;
   const int P = FUSED ? R + 1 : R;                             // pitch of a frame
   const double* S = filtered + (size_t)b * T * P;
   const int k0 = 4 * lane;
@@ -268,7 +297,7 @@ __global__ __launch_bounds__(64) void prune_kernel(const double* __restrict__ fi
     double total = 0.0;
     for (int c = 0; c < nchunks; ++c) {
       const int cn = min(NPY_BUFSIZE, N - c * NPY_BUFSIZE);
-      const double* h = node_sums + ((size_t)b * MAX_CHUNKS + c) * 2;
+      const double* h = GLOBAL_EV ? node_sums + (size_t)b * sum_stride + 2 * c : node_sums + ((size_t)b * MAX_CHUNKS + c) * 2;
       total = total + (cn > PW_BLOCK ? h[0] + h[1] : h[0]);
     }
     mean = total / (double)N;
@@ -286,7 +315,7 @@ __global__ __launch_bounds__(64) void prune_kernel(const double* __restrict__ fi
   const bool own = k0 < R;  // R % 4 == 0: a lane owns 4 bins or none
 
   for (int i = lane; i < 2 * R + 1; i += 64) G[i] = gauss[i];
-  if (FUSED) {
+  if (ZERO_MASK) {
     // the clip's mask is zeroed here (the stores drain while the frames are scanned) instead of by a memset launch in front of the kernel;
     // the launcher guarantees 16-byte pieces (R * T % 16 == 0, aligned base)
     uint4* Z = reinterpret_cast<uint4*>(mask + (size_t)b * R * T);
@@ -390,7 +419,7 @@ __global__ __launch_bounds__(64) void prune_kernel(const double* __restrict__ fi
             for (int s = 0; s < 4; ++s) lastcol[s] = cur[q][s];
           }
         }
-        fs[c] = (short)ne;                                       // (uniform store, as in record)
+        fs[c] = (FsT)ne;                                         // (uniform store, as in record)
         bool ex[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) ex[s] = own && (cur[q][s] > th[s]);    // against the pre-update threshold
@@ -440,8 +469,8 @@ __global__ __launch_bounds__(64) void prune_kernel(const double* __restrict__ fi
 #pragma unroll
       for (int s = 0; s < 4; ++s) cur[q][s] = nxt[q][s];
   }
-  fs[T] = (short)ne;
-  fs[T + 1] = (short)ne;
+  fs[T] = (FsT)ne;
+  fs[T + 1] = (FsT)ne;
   __syncthreads();
 
   // ---- backward pass (peak_extractor.py:206-234)
@@ -471,7 +500,7 @@ __global__ __launch_bounds__(64) void prune_kernel(const double* __restrict__ fi
     // requests for the next iterations go out first: entries of frame c-1, the table cell of frame c-2
     double nv = 0.0; int np = -1;
     if (c >= 1) fetch(st_n, st_c - st_n, nv, np);
-    const short st_nn_raw = c >= 2 ? fs[c - 2] : (short)0;     // consumed (made uniform) at the end of the iteration
+    const FsT st_nn_raw = c >= 2 ? fs[c - 2] : (FsT)0;         // consumed (made uniform) at the end of the iteration
     int my_p = (lane < n) ? (cp & 255) : -1;                   // this frame's bins (lane i = rank i), -1 once pruned
     for (int i = 0; i < n; ++i) {
       const double val = readlane_f64(cv, i);
@@ -498,8 +527,8 @@ __global__ __launch_bounds__(64) void prune_kernel(const double* __restrict__ fi
   }
   __syncthreads();
 
-  // ---- emit: mask (R, T) uint8 was zeroed by the host-side memset on the same stream (FUSED: by this wave, above: fence first)
-  if (FUSED) __threadfence();
+  // ---- emit: mask (R, T) uint8 was zeroed by the launcher's memset on the same stream (ZERO_MASK: by this wave, above: fence first)
+  if (ZERO_MASK) __threadfence();
   uint8_t* M = mask + (size_t)b * R * T;
   int count = 0;
   for (int e = lane; e < ne; e += 64) {
@@ -572,8 +601,8 @@ int mfpa_audfprint_prune(const double* filtered, int B, int R, int T, const doub
   hipStream_t s = mfpa_stream(stream);
   MFPA_HIP(hipMemsetAsync(mask, 0, (size_t)B * R * T, s));
   const size_t lds = sizeof(double) * (2 * R + 2) + (size_t)T * maxpks * (sizeof(double) + sizeof(int)) + sizeof(short) * (T + 2);
-  hipLaunchKernelGGL(prune_kernel<false>, dim3(B), dim3(64), lds, s, filtered, R, T, gauss, a_dec, maxpks, mask, npeaks, (const double*)nullptr,
-                     (const double*)nullptr, 0.0);
+  hipLaunchKernelGGL((prune_kernel<false, false>), dim3(B), dim3(64), lds, s, filtered, R, T, gauss, a_dec, maxpks, mask, npeaks,
+                     (const double*)nullptr, 0ll, (const double*)nullptr, 0.0, (double*)nullptr, (int*)nullptr, (int*)nullptr);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
 }
@@ -595,7 +624,34 @@ int mfpa_audfprint_pick(const double* spec, const double* clip_max, int B, int F
                      1.0, F - 1);
   MFPA_CHECK_LAUNCH();
   const size_t lds = sizeof(double) * (2 * R + 2) + (size_t)T * maxpks * (sizeof(double) + sizeof(int)) + sizeof(short) * (T + 2);
-  hipLaunchKernelGGL(prune_kernel<true>, dim3(B), dim3(64), lds, s, (const double*)work, R, T, gauss, a_dec, maxpks, mask, npeaks, (const double*)sums, clip_max, pole);
+  hipLaunchKernelGGL((prune_kernel<true, false>), dim3(B), dim3(64), lds, s, (const double*)work, R, T, gauss, a_dec, maxpks, mask, npeaks,
+                     (const double*)sums, 0ll, clip_max, pole, (double*)nullptr, (int*)nullptr, (int*)nullptr);
+  MFPA_CHECK_LAUNCH();
+  return MFPA_OK;
+}
+
+int mfpa_audfprint_pick_track(const double* spec, const double* clip_max, int B, int F, int T, double pole, const double* gauss,
+                              double a_dec, int maxpks, double* logs, double* sums, void* events, uint8_t* mask, int32_t* npeaks,
+                              void* stream) {
+  if (B == 0) return MFPA_OK;
+  if (!spec || !clip_max || !gauss || !logs || !sums || !events || !mask || !npeaks || B < 0) return MFPA_EINVAL;
+  const int R = F - 1;
+  if (F < 141 || F > 257 || (R % 4) != 0 || T < 1 || T > MFPA_TRACK_MAX_T || maxpks < 1 || maxpks > MAXP) return MFPA_EINVAL;   // (F >= 141: a half-chunk node spans <= 32 frames)
+  if ((reinterpret_cast<uintptr_t>(events) & 7) != 0) return MFPA_EINVAL;
+  const long long N = (long long)F * T;                        // <= 257 * 16384: int arithmetic in the kernels holds
+  const int nchunks = (int)((N + NPY_BUFSIZE - 1) / NPY_BUFSIZE);
+  hipStream_t s = mfpa_stream(stream);
+  MFPA_HIP(hipMemsetAsync(mask, 0, (size_t)B * R * T, s));
+  const size_t lds1 = sizeof(double) * (NPY_BUFSIZE / 2 + 8 + HEAP + 128 * 3);
+  hipLaunchKernelGGL(prep_sum_kernel, dim3(B, 2 * nchunks), dim3(SPLIT_THREADS), lds1, s, spec, F, T, clip_max, 1, logs, 1, sums,
+                     (long long)(2 * nchunks), 1.0, F - 1);
+  MFPA_CHECK_LAUNCH();
+  const size_t cap = (size_t)T * maxpks;
+  double* ev = reinterpret_cast<double*>(events);              // [B][cap]
+  int* ep = reinterpret_cast<int*>(ev + (size_t)B * cap);      // [B][cap]
+  int* fs = ep + (size_t)B * cap;                              // [B][T + 2]
+  hipLaunchKernelGGL((prune_kernel<true, true>), dim3(B), dim3(64), sizeof(double) * (2 * R + 2), s, (const double*)logs, R, T, gauss, a_dec, maxpks,
+                     mask, npeaks, (const double*)sums, (long long)(2 * nchunks), clip_max, pole, ev, ep, fs);
   MFPA_CHECK_LAUNCH();
   return MFPA_OK;
 }

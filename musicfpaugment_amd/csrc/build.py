@@ -25,7 +25,6 @@ COMMON = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno
 # multiply / add sequence: no FMA contraction there.
 PER_FILE = {
     "audfprint.hip": ["-ffp-contract=off"],
-    "audfprint_track.hip": ["-ffp-contract=off"],
     "dejavu.hip": ["-ffp-contract=off"],
     "nplog.hip": ["-ffp-contract=off"],
 }

@@ -7,6 +7,10 @@
 
 #define MFPA_WAVE 64
 
+// Most frames of a whole track (mfpa_audfprint_pick_track, mfpa_audfprint_landmarks_track): frame times below 2^14 are stored in the
+// hash table without wrapping (afp/audfprint/hash_table.py:55 of the reference)
+constexpr int MFPA_TRACK_MAX_T = 16384;
+
 #define MFPA_CHECK_LAUNCH()                                   \
   do {                                                        \
     hipError_t e__ = hipGetLastError();                       \

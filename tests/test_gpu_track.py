@@ -1,4 +1,4 @@
-"""GPU: Audfprint on whole tracks (csrc/audfprint_track.hip, Audfprint_peaks(whole_tracks=True), create_fp_database*(whole_tracks=True)).
+"""GPU: Audfprint on whole tracks (csrc/audfprint.hip and csrc/hashes.hip, Audfprint_peaks(whole_tracks=True), create_fp_database*(whole_tracks=True)).
 
 Every comparison is EQUALITY: the path is integer or bit-exact float64 by construction, as for the clip kernels.
   1. the same answers as the clip kernels wherever both apply (pick and landmarks, every tile seam);
@@ -77,6 +77,31 @@ def test_pick_track_equals_the_clip_kernels(clip_masks, which, frames):
     if frames <= 512:                                            # the fused clip picker too
         m2, n2 = _ops().audfprint_pick(mag, cmax)
         assert torch.equal(got_mask, m2) and torch.equal(got_n, n2)
+
+
+def test_pick_track_equals_prepare_plus_prune_on_short_ragged_and_silent_clips():
+    """The five batches of test_fused_pick_equals_prepare_plus_prune_bit_for_bit (tests/test_gpu_peaks.py) and one of 1280 samples
+    through the pruner's global-workspace form: frame counts that are no multiple of four, a silent clip (denom == 0), a half-silent
+    one, the launcher's memset in place of the kernel's own zeroing; exactly ten frames (2304 samples: 2304 // 256 + 1) and six (1280
+    samples: the `T < 10` side of the seed over the first ten frames).  Identical masks and counts; and at least one clip of every
+    batch of more than ten frames has peaks, so that two empty masks cannot pass for coverage.  With ten frames or fewer the pruner
+    seeds its threshold with the maximum over every frame the clip has, so such clips may find no peak at all."""
+    ops = _ops()
+    for n, B in ((64000, 12), (24000, 5), (2304, 3), (8000 + 77, 4), (130560, 2), (1280, 3)):
+        wav = np.stack([synth.clip(700 + i, n=n, tonal=(i % 3 != 1)) for i in range(B)])
+        if B > 3:
+            wav[1] = 0.0
+            wav[2, : n // 2] = 0.0
+        mag, cmax = ops.stft_mag(torch.from_numpy(wav).cuda(), torch.float64)
+        assert mag.shape[2] == n // 256 + 1
+        a_dec = ops.audfprint_a_dec()
+        want_mask, want_n = ops.audfprint_prune(ops.audfprint_prepare(mag, cmax, mean_order=1, denom_is_clip_max=True), a_dec)
+        got_mask, got_n = ops.audfprint_pick_track(mag, cmax, a_dec)
+        assert torch.equal(got_mask, want_mask) and torch.equal(got_n, want_n), (n, B)
+        if mag.shape[2] > 10:
+            assert int(want_n.max()) > 0, (n, B)
+        if B > 3:
+            assert int(got_n[1]) == 0                            # the silent clip
 
 
 def _landmarks_both(mask, cap=8192):

@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from musicfpaugment_amd.csrc import isa_scan
 
 _LABEL = re.compile(r"^[0-9a-f]+ <([^>]+)>:")
-_PAD = re.compile(r"^(s_nop|s_code_end|v_nop|\.\.\.)")
+PAD = re.compile(r"^(s_nop|s_code_end|v_nop|\.\.\.)")
 _GETPC = re.compile(r"^s_getpc_b64 s\[(\d+):(\d+)\]")
 _NOTE_KEYS = {".vgpr_count": "vgpr", ".agpr_count": "agpr", ".sgpr_count": "sgpr", ".private_segment_fixed_size": "scratch",
               ".group_segment_fixed_size": "lds", ".kernarg_segment_size": "kernarg"}
@@ -31,7 +31,7 @@ def _tool(name):
     return os.path.join(os.path.dirname(isa_scan._objdump()), name)
 
 
-def _demangle(names):
+def demangle(names):
     filt = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
     if not filt or not names:             # no demangler: the mangled names compare just as well
         return {n: n for n in names}
@@ -39,7 +39,7 @@ def _demangle(names):
     return dict(zip(names, out))
 
 
-def _resources(path):
+def resources(path):
     """kernel symbol -> {vgpr, agpr, sgpr, scratch, lds, kernarg} from the AMDGPU metadata note"""
     txt = subprocess.run([_tool("llvm-readelf"), "--notes", path], capture_output=True, text=True, check=True).stdout
     res, cur = {}, {}
@@ -62,7 +62,7 @@ def kernels(paths):
                 f = os.path.join(tmp, f"{len(out)}_{k}.co")
                 with open(f, "wb") as fh:
                     fh.write(co)
-                res = _resources(f)
+                res = resources(f)
                 txt = subprocess.run([isa_scan._objdump(), "-d", f], capture_output=True, text=True, check=True).stdout
                 body, sym = {}, None
                 for line in txt.splitlines():
@@ -72,10 +72,10 @@ def kernels(paths):
                         body[sym] = []
                     elif sym and line.startswith("\t"):
                         body[sym].append(" ".join(line.split("//")[0].split()))
-                names = _demangle(list(body))
+                names = demangle(list(body))
                 for s, nm in names.items():
                     ins = body[s]
-                    while ins and _PAD.match(ins[-1]):
+                    while ins and PAD.match(ins[-1]):
                         ins.pop()
                     for j, line in enumerate(ins):
                         m = _GETPC.match(line)

@@ -1209,6 +1209,39 @@ int mfpa_phase_vocoder(const double* spec, int B, int n_frames, const double* ra
  * n_frames < 1 or > MFPA_VOCODER_MAX_FRAMES, a rate that is not finite or not positive, a result above MFPA_VOCODER_MAX_FRAMES. */
 int mfpa_vocoder_frames(int n_frames, double rate, int* n_out);
 
+/* ---------------------------------------------------------------------------------------
+ * Recursive filters (csrc/iir.hip): scipy.signal.sosfilt -- a cascade of S second-order sections in transposed direct form II, one
+ * filter for the batch or one per row.  Additive to ABI 47.
+ *
+ * Section s has the coefficients b0 b1 b2 a0 a1 a2 with a0 == 1 (the caller normalises; a0 is not read) and the state (z1, z2);
+ * sample by sample, the output of section s being the input of section s + 1:
+ *   y = b0 x + z1;   z1 = (b1 x - a1 y) + z2;   z2 = b2 x - a2 y
+ * State and arithmetic are float64, every product and sum rounded on its own (no fused multiply-add), in this order.  The samples
+ * are float32 (x_f64 = 0) or float64 (x_f64 = 1); the float32 output is the float64 result rounded once.
+ *   x, y    (B, T) on the device, element aligned (4 or 8 bytes), not overlapping
+ *   sos     (S, 6) with sos_per_row = 0, (B, S, 6) with sos_per_row = 1, float64 on the device.  The values are NOT checked (they
+ *           live on the device): an unstable or non-finite section gives what float64 gives
+ *   apply   NULL, or B bytes on the device: row b with apply[b] == 0 is copied through bit for bit, and its final state is its
+ *           initial state
+ *   zi, zf  NULL, or (B, S, 2) float64 on the device: scipy's initial state (zeros without zi) and the state after sample T - 1
+ *   clamp   1: the output is clamped to [-1, 1] before it is stored (torchaudio.functional.lfilter's default); a NaN stays a NaN
+ *   work    work_len >= mfpa_sosfilt_work(B, S, sos_per_row) float64 on the device: per filter and section 64 2x2 matrices, the
+ *           powers A^(16 j), j = 1..64, of the section's state matrix A = [[-a1, 1], [-a2, 0]], written by a setup launch that runs
+ *           the section's own homogeneous recurrence from the unit states (NOT by squaring A: DESIGN.md section 3.15)
+ * One wavefront owns one row and walks it in chunks of 64 lanes x 16 samples: every lane filters its 16 samples from zero state,
+ * a shuffle scan over the lanes' end states (with those powers) plus the carry of the chunks before gives each lane its true
+ * start state, and the lane filters its samples again from there.  No atomics; a row's bits do not depend on B, on the row's
+ * position or on its neighbours.  -0.0 follows the formula: the identity section turns a -0.0 sample into +0.0, like scipy.
+ * MFPA_EINVAL before any launch, no pointer dereferenced on the host: B < 0 or B > 65535, T < 1 or T > 2^30, S < 1 or
+ * S > MFPA_SOS_MAX_SECTIONS, x_f64 / sos_per_row / clamp other than 0 or 1, work_len too short, and with B > 0 a null x, y, sos or
+ * work or a misaligned pointer.  B == 0: MFPA_OK, no launch. */
+#define MFPA_SOS_MAX_SECTIONS 8
+int mfpa_sosfilt(const void* x, int x_f64, int B, long long T, const double* sos, int S, int sos_per_row, const unsigned char* apply,
+                 const double* zi, double* zf, int clamp, double* work, long long work_len, void* y, void* stream);
+/* HOST function, no GPU work: *work_len = F * S * 256 doubles, F = B filters with sos_per_row = 1, else 1 (0 for B == 0).
+ * MFPA_EINVAL: a null pointer, or B, S or sos_per_row outside mfpa_sosfilt's rules. */
+int mfpa_sosfilt_work(int B, int S, int sos_per_row, long long* work_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -220,6 +220,9 @@ _SIGNATURES = {
     "mfpa_istft_envelope_min": ([c_void_p, c_int, c_int, c_void_p], c_int),
     "mfpa_phase_vocoder": ([c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
     "mfpa_vocoder_frames": ([c_int, c_double, c_void_p], c_int),
+    "mfpa_sosfilt": ([c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                      c_longlong, c_void_p, c_void_p], c_int),
+    "mfpa_sosfilt_work": ([c_int, c_int, c_int, c_void_p], c_int),
 }
 
 

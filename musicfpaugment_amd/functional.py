@@ -1,0 +1,168 @@
+"""Substitutes for torchaudio.functional's filtering: `lfilter`, `biquad` and the `*_biquad` family, with torchaudio's signatures,
+(..., T) in and out on the input's device like transforms.Resample.  The recurrence runs in csrc/iir.hip (ops.sosfilt); there is no
+CPU fallback.
+
+Two things differ from torchaudio, on purpose:
+  * torchaudio filters in the input's dtype; this filters in float64 whatever the input and rounds a float32 output once.  Parity
+    with torchaudio itself is therefore unpinned (torchaudio is not installed where this is tested);
+  * the pinned reference is scipy: the output is scipy.signal.sosfilt's in float64 within a few of scipy's own rounding errors
+    (tests/test_gpu_iir.py), and the designs meet their defining gains under scipy.signal.freqz (tests/test_iir_oracle.py).
+
+The coefficient designs are the public Audio-EQ-Cookbook formulas (R. Bristow-Johnson) in the form torchaudio uses, as pure host
+functions in float64: `biquad_coefficients(kind, sample_rate, freq, Q, gain_db)`.  Orders above 2 go through ops.sosfilt as
+second-order sections; there is no tf2sos here.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import MfpaError
+
+BIQUAD_KINDS = ("lowpass", "highpass", "bandpass", "bandpass_skirt", "bandreject", "allpass", "peaking", "lowshelf", "highshelf")
+
+
+def biquad_coefficients(kind: str, sample_rate: float, freq: float, Q: float, gain_db: Optional[float] = None) -> np.ndarray:
+    """(b0, b1, b2, a0, a1, a2) of one cookbook biquad, float64, not normalised (a0 is the cookbook's).  `kind` is one of
+    BIQUAD_KINDS: "bandpass" has a 0 dB peak, "bandpass_skirt" a constant skirt gain (peak gain Q); "peaking", "lowshelf" and
+    "highshelf" need gain_db.  ValueError: an unknown kind, a frequency outside (0, sample_rate / 2), Q <= 0, a missing or
+    non-finite gain."""
+    if kind not in BIQUAD_KINDS:
+        raise ValueError(f"kind must be one of {BIQUAD_KINDS}, got {kind!r}")
+    sample_rate, freq, Q = float(sample_rate), float(freq), float(Q)
+    if not (math.isfinite(sample_rate) and sample_rate > 0.0):
+        raise ValueError(f"sample_rate must be positive, got {sample_rate}")
+    if not 0.0 < freq < sample_rate / 2:
+        raise ValueError(f"the frequency must lie in (0, sample_rate / 2 = {sample_rate / 2}), got {freq}")
+    if not (math.isfinite(Q) and Q > 0.0):
+        raise ValueError(f"Q must be positive, got {Q}")
+    w0 = 2.0 * math.pi * freq / sample_rate
+    cs, sn = math.cos(w0), math.sin(w0)
+    alpha = sn / (2.0 * Q)
+    if kind in ("peaking", "lowshelf", "highshelf"):
+        if gain_db is None or not math.isfinite(float(gain_db)):
+            raise ValueError(f"{kind} needs a finite gain_db")
+        A = math.exp(float(gain_db) / 40.0 * math.log(10.0))
+    if kind == "lowpass":
+        c = ((1.0 - cs) / 2.0, 1.0 - cs, (1.0 - cs) / 2.0, 1.0 + alpha, -2.0 * cs, 1.0 - alpha)
+    elif kind == "highpass":
+        c = ((1.0 + cs) / 2.0, -1.0 - cs, (1.0 + cs) / 2.0, 1.0 + alpha, -2.0 * cs, 1.0 - alpha)
+    elif kind in ("bandpass", "bandpass_skirt"):
+        t = sn / 2.0 if kind == "bandpass_skirt" else alpha
+        c = (t, 0.0, -t, 1.0 + alpha, -2.0 * cs, 1.0 - alpha)
+    elif kind == "bandreject":
+        c = (1.0, -2.0 * cs, 1.0, 1.0 + alpha, -2.0 * cs, 1.0 - alpha)
+    elif kind == "allpass":
+        c = (1.0 - alpha, -2.0 * cs, 1.0 + alpha, 1.0 + alpha, -2.0 * cs, 1.0 - alpha)
+    elif kind == "peaking":
+        c = (1.0 + alpha * A, -2.0 * cs, 1.0 - alpha * A, 1.0 + alpha / A, -2.0 * cs, 1.0 - alpha / A)
+    else:
+        t1, t2, t3 = 2.0 * math.sqrt(A) * alpha, (A - 1.0) * cs, (A + 1.0) * cs
+        if kind == "lowshelf":
+            c = (A * ((A + 1.0) - t2 + t1), 2.0 * A * ((A - 1.0) - t3), A * ((A + 1.0) - t2 - t1),
+                 (A + 1.0) + t2 + t1, -2.0 * ((A - 1.0) + t3), (A + 1.0) + t2 - t1)
+        else:
+            c = (A * ((A + 1.0) + t2 + t1), -2.0 * A * ((A - 1.0) + t3), A * ((A + 1.0) + t2 - t1),
+                 (A + 1.0) - t2 + t1, 2.0 * ((A - 1.0) - t3), (A + 1.0) - t2 - t1)
+    return np.array(c, dtype=np.float64)
+
+
+def _filter(waveform: torch.Tensor, sos: np.ndarray, clamp: bool, who: str) -> torch.Tensor:
+    """sos (S, 6) for every row or (F, S, 6) for the F rows of the last but one dimension."""
+    sos = ops.sos_normalized(sos)                                            # the refusals need no GPU
+    if not isinstance(waveform, torch.Tensor) or waveform.dim() < 1 or waveform.dtype not in (torch.float32, torch.float64):
+        raise ValueError("waveform must be a float32 or float64 tensor (..., T)")
+    x = waveform
+    if not x.is_cuda:
+        if not torch.cuda.is_available():
+            raise MfpaError(f"{who} computes on the MI355X and none is present; no CPU fallback")
+        x = x.cuda()
+    lead, T = x.shape[:-1], x.shape[-1]
+    rows = x.reshape(-1, T)
+    if sos.ndim == 3:
+        sos = np.ascontiguousarray(np.broadcast_to(sos, (rows.shape[0] // sos.shape[0],) + sos.shape).reshape(-1, *sos.shape[1:]))
+    with torch.cuda.device(x.device):
+        y = ops.sosfilt(rows, sos, clamp=clamp)
+    return y.reshape(*lead, T).to(waveform.device)
+
+
+def _coeff_rows(c, name: str) -> np.ndarray:
+    c = np.array(c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c, dtype=np.float64)
+    if c.ndim not in (1, 2) or c.shape[-1] < 1:
+        raise ValueError(f"{name} must be (num_order + 1,) or (num_filters, num_order + 1), got {c.shape}")
+    return c
+
+
+def lfilter(waveform: torch.Tensor, a_coeffs, b_coeffs, clamp: bool = True, batching: bool = True) -> torch.Tensor:
+    """torchaudio.functional.lfilter (note its order: the DENOMINATOR first) for filters of order up to 2, lower delays first.
+    Coefficients (num_order + 1,) filter every row; (num_filters, num_order + 1) with batching=True filter the rows of a
+    (..., num_filters, T) waveform each with its own filter, and with batching=False every input row with every filter:
+    (..., T) -> (..., num_filters, T).  Longer coefficient vectors are a NotImplementedError: give them to ops.sosfilt as
+    second-order sections."""
+    a, b = _coeff_rows(a_coeffs, "a_coeffs"), _coeff_rows(b_coeffs, "b_coeffs")
+    if a.shape != b.shape:
+        raise ValueError(f"a_coeffs and b_coeffs must have the same shape, got {a.shape} and {b.shape}")
+    if a.shape[-1] > 3:
+        raise NotImplementedError(f"lfilter takes orders up to 2 (3 coefficients), got {a.shape[-1]}: factor the filter into "
+                                  "second-order sections and call ops.sosfilt")
+    pad = [(0, 0)] * (a.ndim - 1) + [(0, 3 - a.shape[-1])]
+    sos = np.concatenate([np.pad(b, pad), np.pad(a, pad)], axis=-1)           # (6,) or (F, 6)
+    if sos.ndim == 1:
+        return _filter(waveform, sos[None], clamp, "lfilter")
+    sos = sos[:, None, :]                                                     # (F, 1, 6)
+    if not isinstance(waveform, torch.Tensor) or waveform.dim() < 1:
+        raise ValueError("waveform must be a float32 or float64 tensor (..., T)")
+    if not batching:
+        waveform = waveform.unsqueeze(-2).expand(*waveform.shape[:-1], sos.shape[0], waveform.shape[-1])
+    elif waveform.dim() < 2 or waveform.shape[-2] != sos.shape[0]:
+        raise ValueError(f"with batching, {sos.shape[0]} filters need a waveform (..., {sos.shape[0]}, T)")
+    return _filter(waveform, sos, clamp, "lfilter")
+
+
+def biquad(waveform: torch.Tensor, b0: float, b1: float, b2: float, a0: float, a1: float, a2: float) -> torch.Tensor:
+    """torchaudio.functional.biquad: lfilter of one second-order section, clamped to [-1, 1] like torchaudio's."""
+    return _filter(waveform, np.array([[float(b0), float(b1), float(b2), float(a0), float(a1), float(a2)]]), True, "biquad")
+
+
+def _design(waveform, who: str, kind: str, sample_rate, freq, Q, gain_db=None) -> torch.Tensor:
+    return _filter(waveform, biquad_coefficients(kind, sample_rate, freq, Q, gain_db)[None], True, who)
+
+
+def lowpass_biquad(waveform: torch.Tensor, sample_rate: int, cutoff_freq: float, Q: float = 0.707) -> torch.Tensor:
+    return _design(waveform, "lowpass_biquad", "lowpass", sample_rate, cutoff_freq, Q)
+
+
+def highpass_biquad(waveform: torch.Tensor, sample_rate: int, cutoff_freq: float, Q: float = 0.707) -> torch.Tensor:
+    return _design(waveform, "highpass_biquad", "highpass", sample_rate, cutoff_freq, Q)
+
+
+def bandpass_biquad(waveform: torch.Tensor, sample_rate: int, central_freq: float, Q: float = 0.707,
+                    const_skirt_gain: bool = False) -> torch.Tensor:
+    return _design(waveform, "bandpass_biquad", "bandpass_skirt" if const_skirt_gain else "bandpass", sample_rate, central_freq, Q)
+
+
+def bandreject_biquad(waveform: torch.Tensor, sample_rate: int, central_freq: float, Q: float = 0.707) -> torch.Tensor:
+    return _design(waveform, "bandreject_biquad", "bandreject", sample_rate, central_freq, Q)
+
+
+def allpass_biquad(waveform: torch.Tensor, sample_rate: int, central_freq: float, Q: float = 0.707) -> torch.Tensor:
+    return _design(waveform, "allpass_biquad", "allpass", sample_rate, central_freq, Q)
+
+
+def equalizer_biquad(waveform: torch.Tensor, sample_rate: int, center_freq: float, gain: float, Q: float = 0.707) -> torch.Tensor:
+    """A peaking equaliser: `gain` dB at center_freq."""
+    return _design(waveform, "equalizer_biquad", "peaking", sample_rate, center_freq, Q, gain)
+
+
+def bass_biquad(waveform: torch.Tensor, sample_rate: int, gain: float, central_freq: float = 100, Q: float = 0.707) -> torch.Tensor:
+    """A low shelf: `gain` dB below central_freq."""
+    return _design(waveform, "bass_biquad", "lowshelf", sample_rate, central_freq, Q, gain)
+
+
+def treble_biquad(waveform: torch.Tensor, sample_rate: int, gain: float, central_freq: float = 3000, Q: float = 0.707) -> torch.Tensor:
+    """A high shelf: `gain` dB above central_freq."""
+    return _design(waveform, "treble_biquad", "highshelf", sample_rate, central_freq, Q, gain)

@@ -21,6 +21,101 @@ using mfpa_tile::f32x4;
 
 constexpr int RED_BLOCKS = 1024;
 
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// ------------------------------------------------------------------ the BatchNorm + ReLU (+ dropout) backward of one element, written once
+// Every kernel below that reduces or applies that backward -- on its own or fused into the pool / OutConv backward -- goes through these,
+// so the fused and unfused forms of the step stay bit-compatible by construction.
+struct BnCh4 {                       // one channel quad's constants of the forward: y = relu(z*scale+shift), xhat = (z-mean)*invstd
+  f32x4 scale, shift, mean, invstd;
+};
+__device__ __forceinline__ BnCh4 bn_ld(const float* scale, const float* shift, const float* mean, const float* invstd, int c) {
+  return BnCh4{ld4(scale + c), ld4(shift + c), ld4(mean + c), ld4(invstd + c)};
+}
+struct BnCoef4 {                     // ... and of the backward: dz = ka*g - kb - kc*xhat (bn_bwd_coef's [3][C])
+  f32x4 ka, kb, kc;
+};
+__device__ __forceinline__ BnCoef4 bn_coef_ld(const float* coef, int C, int c) {
+  return BnCoef4{ld4(coef + c), ld4(coef + C + c), ld4(coef + 2 * C + c)};
+}
+// g = d * [z*scale+shift > 0], then the stateless dropout mask of element idx (drop_thresh 0: no dropout)
+__device__ __forceinline__ float bn_gate(float d, float z, const BnCh4& ch, int k, unsigned drop_seed, unsigned drop_thresh, float drop_scale,
+                                         unsigned long long idx) {
+  float g = (z * ch.scale[k] + ch.shift[k] > 0.f) ? d : 0.f;
+  if (drop_thresh) g = mfpa_keep(drop_seed, drop_thresh, idx) ? g * drop_scale : 0.f;
+  return g;
+}
+__device__ __forceinline__ float bn_xhat(float z, const BnCh4& ch, int k) { return (z - ch.mean[k]) * ch.invstd[k]; }
+__device__ __forceinline__ float bn_dz(const BnCoef4& co, int k, float g, float xh) { return co.ka[k] * g - co.kb[k] - co.kc[k] * xh; }
+
+// one pixel's channel quad (incoming gradient d, raw activation z, first element idx0) into the backward's pair sums {sum g, sum g*xhat}:
+// float64 inside a workgroup (the two sums cancel heavily, and a float32 running sum over a row's ~500 pixels would put its rounding,
+// relative to sum |g|, into dgamma / dbeta / dz of every engine precision)
+__device__ __forceinline__ void bn_sums4(double (&s0)[4], double (&s1)[4], const f32x4& d, const f32x4& z, const BnCh4& ch, unsigned drop_seed,
+                                         unsigned drop_thresh, float drop_scale, unsigned long long idx0) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float g = bn_gate(d[k], z[k], ch, k, drop_seed, drop_thresh, drop_scale, idx0 + k);
+    s0[k] += (double)g;
+    s1[k] += (double)g * (double)bn_xhat(z[k], ch, k);
+  }
+}
+// ... and through the backward formula: its dz
+__device__ __forceinline__ f32x4 bn_dz4(const f32x4& d, const f32x4& z, const BnCh4& ch, const BnCoef4& co, unsigned drop_seed,
+                                        unsigned drop_thresh, float drop_scale, unsigned long long idx0) {
+  f32x4 o;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    o[k] = bn_dz(co, k, bn_gate(d[k], z[k], ch, k, drop_seed, drop_thresh, drop_scale, idx0 + k), bn_xhat(z[k], ch, k));
+  return o;
+}
+
+__device__ __forceinline__ bf16x4 to_bf16x4(const f32x4& v) {
+  bf16x4 h;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) h[k] = (__bf16)v[k];
+  return h;
+}
+__device__ __forceinline__ void st_bf16x4(__bf16* dst, const f32x4& v) { *reinterpret_cast<bf16x4*>(dst) = to_bf16x4(v); }
+
+// Workgroup combine of per-thread pair sums: thread t holds s0[4], s1[4] of channel quad t % lanes for pixel-row t / lanes (256 % lanes == 0).
+// The row-0 thread of each quad (t < lanes: the owner) adds rows 1 .. rows-1 to its own in ascending order -- fixed, so deterministic -- and
+// gets true; it then stores with one of the two forms below.  A caller that combines again must __syncthreads() first.
+__device__ __forceinline__ bool wg_pair_sums(double (&s0)[4], double (&s1)[4], int lanes, int rows) {
+  __shared__ double sh[256 * 8];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    sh[threadIdx.x * 8 + k] = s0[k];
+    sh[threadIdx.x * 8 + 4 + k] = s1[k];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x >= lanes) return false;
+  for (int r = 1; r < rows; ++r)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      s0[k] += sh[(r * lanes + threadIdx.x) * 8 + k];
+      s1[k] += sh[(r * lanes + threadIdx.x) * 8 + 4 + k];
+    }
+  return true;
+}
+// this workgroup's row of `part` (rows x 2 x C float32, the layout of the convolutions' stats_part, finished in float64 by
+// conv_stats_rows_kernel): the float64 sums are rounded to float32 here, once
+__device__ __forceinline__ void st_part_row(float* __restrict__ part, int C, int cq, const double (&s0)[4], const double (&s1)[4]) {
+  float* row = part + (size_t)blockIdx.x * 2 * C;
+  *reinterpret_cast<f32x4*>(row + 4 * cq) = f32x4{(float)s0[0], (float)s0[1], (float)s0[2], (float)s0[3]};
+  *reinterpret_cast<f32x4*>(row + C + 4 * cq) = f32x4{(float)s1[0], (float)s1[1], (float)s1[2], (float)s1[3]};
+}
+// partial[(blk*C + c)*NV + v]: NV float64 sums per channel, as they are
+template <int NV>
+__device__ __forceinline__ void st_partial(double* __restrict__ partial, int C, int cq, const double (&s0)[4], const double (&s1)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    double* dst = partial + ((size_t)blockIdx.x * C + 4 * cq + k) * NV;
+    dst[0] = s0[k];
+    if (NV == 2) dst[1] = s1[k];
+  }
+}
+
 // ------------------------------------------------------------------ per-channel sums over pixels
 // partial[(blk*C + c)*NV + v]: NV float64 sums per channel.  MODE 0: {sum z, sum z^2} (BN statistics);
 // MODE 1: {sum g, sum g*xhat} with g = dy*[z*scale+shift > 0], xhat = (z-mean)*invstd (BN backward);
@@ -39,18 +134,12 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const float* __restric
   const int lanes = C4 < 256 ? C4 : 256;          // lanes across channel quads
   const int rows = 256 / lanes;                   // pixels in flight per block
   const int cq0 = threadIdx.x % lanes, prow = threadIdx.x / lanes;
-  __shared__ double sh[256 * 8];
   for (int cq = cq0; cq < C4; cq += lanes) {
     double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
-    f32x4 sc = {0, 0, 0, 0}, sf = {0, 0, 0, 0}, mu = {0, 0, 0, 0}, is = {0, 0, 0, 0};
-    if (MODE == 1) {
-      sc = *reinterpret_cast<const f32x4*>(scale + 4 * cq);
-      sf = *reinterpret_cast<const f32x4*>(shift + 4 * cq);
-      mu = *reinterpret_cast<const f32x4*>(mean + 4 * cq);
-      is = *reinterpret_cast<const f32x4*>(invstd + 4 * cq);
-    }
+    BnCh4 ch = {};
+    if (MODE == 1) ch = bn_ld(scale, shift, mean, invstd, 4 * cq);
     for (long long p = (long long)blockIdx.x * rows + prow; p < npix; p += (long long)gridDim.x * rows) {
-      const f32x4 v = (MODE == 0) ? mfpa_ld_act4(x, (size_t)p * C + 4 * cq, z16) : *reinterpret_cast<const f32x4*>(x + (size_t)p * C + 4 * cq);
+      const f32x4 v = (MODE == 0) ? mfpa_ld_act4(x, (size_t)p * C + 4 * cq, z16) : ld4(x + (size_t)p * C + 4 * cq);
       if (MODE == 0) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -58,41 +147,15 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const float* __restric
           s1[k] += (double)v[k] * (double)v[k];
         }
       } else if (MODE == 1) {
-        const f32x4 zz = mfpa_ld_act4(z, (size_t)p * C + 4 * cq, z16);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float g = (zz[k] * sc[k] + sf[k] > 0.f) ? v[k] : 0.f;
-          if (drop_thresh) g = mfpa_keep(drop_seed, drop_thresh, (unsigned long long)p * C + 4 * cq + k) ? g * drop_scale : 0.f;
-          const float xh = (zz[k] - mu[k]) * is[k];
-          s0[k] += (double)g;
-          s1[k] += (double)g * (double)xh;
-        }
+        bn_sums4(s0, s1, v, mfpa_ld_act4(z, (size_t)p * C + 4 * cq, z16), ch, drop_seed, drop_thresh, drop_scale,
+                 (unsigned long long)p * C + 4 * cq);
       } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) s0[k] += (double)v[k];
       }
     }
     // combine the `rows` pixel-rows of this block for channel quad cq
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      sh[threadIdx.x * 8 + k] = s0[k];
-      sh[threadIdx.x * 8 + 4 + k] = s1[k];
-    }
-    __syncthreads();
-    if (prow == 0) {
-      for (int r = 1; r < rows; ++r)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          s0[k] += sh[(r * lanes + cq0) * 8 + k];
-          s1[k] += sh[(r * lanes + cq0) * 8 + 4 + k];
-        }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        double* dst = partial + ((size_t)blockIdx.x * C + 4 * cq + k) * NV;
-        dst[0] = s0[k];
-        if (NV == 2) dst[1] = s1[k];
-      }
-    }
+    if (wg_pair_sums(s0, s1, lanes, rows)) st_partial<NV>(partial, C, cq, s0, s1);
     __syncthreads();
   }
 }
@@ -104,6 +167,22 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+// The opening of every finish kernel: c = this wavefront's channel, s[v] = sum over the nblk blocks of partial[(blk*C + c)*NV + v];
+// true for the one lane that finalises channel c.
+template <int NV>
+__device__ __forceinline__ bool wave_channel_sums(const double* __restrict__ partial, int nblk, int C, int& c, double (&s)[NV]) {
+  c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (c >= C) return false;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) s[v] = 0;
+  for (int b = lane; b < nblk; b += 64)
+#pragma unroll
+    for (int v = 0; v < NV; ++v) s[v] += partial[((size_t)b * C + c) * NV + v];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) s[v] = wave_sum_d(s[v]);
+  return lane == 0;
+}
 
 // BN statistics finish: mean, biased var -> invstd, fused (scale, shift); running stats with momentum
 // (unbiased variance), exactly nn.BatchNorm2d in train mode (training/unet.py:17,20).
@@ -114,18 +193,11 @@ __global__ __launch_bounds__(256) void bn_stats_finish_kernel(const double* __re
                                                               float* __restrict__ invstd, float* __restrict__ scale,
                                                               float* __restrict__ shift, float* __restrict__ running_mean,
                                                               float* __restrict__ running_var) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (c >= C) return;
-  double s = 0, ss = 0;
-  for (int b = lane; b < nblk; b += 64) {
-    s += partial[((size_t)b * C + c) * 2];
-    ss += partial[((size_t)b * C + c) * 2 + 1];
-  }
-  s = wave_sum_d(s);
-  ss = wave_sum_d(ss);
-  if (lane) return;
-  const double m = s / count;
-  double var = ss / count - m * m;
+  int c;
+  double s[2];                                     // {sum z, sum z^2}
+  if (!wave_channel_sums<2>(partial, nblk, C, c, s)) return;
+  const double m = s[0] / count;
+  double var = s[1] / count - m * m;
   if (var < 0) var = 0;
   const double is = 1.0 / sqrt(var + (double)eps);
   mean[c] = (float)m;
@@ -142,41 +214,34 @@ __global__ __launch_bounds__(256) void bn_stats_finish_kernel(const double* __re
 
 // BN backward finish: dgamma = sum g*xhat, dbeta = sum g; coefficients so that
 // dz = ka*g - kb - kc*xhat  with ka = gamma*invstd, kb = ka*dbeta/N, kc = ka*dgamma/N.
+// LOCAL sums (lsg, lsgx) are this rank's dgamma / dbeta (the gradient all-reduce adds the ranks); GLOBAL sums (gsg, gsgx) over `count` pixels
+// of all ranks give the mean terms of the input gradient.  On one GPU they are the same pair.
+__device__ __forceinline__ void bn_bwd_coef(int c, int C, double lsg, double lsgx, double gsg, double gsgx, double count,
+                                            const float* __restrict__ gamma, const float* __restrict__ invstd, float* __restrict__ dgamma,
+                                            float* __restrict__ dbeta, float* __restrict__ coef /* [3][C] */) {
+  dgamma[c] = (float)lsgx;
+  dbeta[c] = (float)lsg;
+  const double ka = (double)gamma[c] * (double)invstd[c];
+  coef[c] = (float)ka;
+  coef[C + c] = (float)(ka * gsg / count);
+  coef[2 * C + c] = (float)(ka * gsgx / count);
+}
+
 __global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const double* __restrict__ partial, int nblk, int C,
                                                             double count, const float* __restrict__ gamma,
                                                             const float* __restrict__ invstd, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta, float* __restrict__ coef /* [3][C] */) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (c >= C) return;
-  double sg = 0, sgx = 0;
-  for (int b = lane; b < nblk; b += 64) {
-    sg += partial[((size_t)b * C + c) * 2];
-    sgx += partial[((size_t)b * C + c) * 2 + 1];
-  }
-  sg = wave_sum_d(sg);
-  sgx = wave_sum_d(sgx);
-  if (lane) return;
-  dgamma[c] = (float)sgx;
-  dbeta[c] = (float)sg;
-  const double ka = (double)gamma[c] * (double)invstd[c];
-  coef[c] = (float)ka;
-  coef[C + c] = (float)(ka * sg / count);
-  coef[2 * C + c] = (float)(ka * sgx / count);
+  int c;
+  double s[2];                                     // {sum g, sum g*xhat}
+  if (wave_channel_sums<2>(partial, nblk, C, c, s)) bn_bwd_coef(c, C, s[0], s[1], s[0], s[1], count, gamma, invstd, dgamma, dbeta, coef);
 }
 
 // SyncBN building blocks: per-channel partial pairs -> one [C][2] float64 row (the caller all-reduces it across ranks) ...
 __global__ __launch_bounds__(256) void pair_sums_kernel(const double* __restrict__ partial, int nblk, int C,
                                                         double* __restrict__ sums) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (c >= C) return;
-  double s = 0, ss = 0;
-  for (int b = lane; b < nblk; b += 64) {
-    s += partial[((size_t)b * C + c) * 2];
-    ss += partial[((size_t)b * C + c) * 2 + 1];
-  }
-  s = wave_sum_d(s);
-  ss = wave_sum_d(ss);
-  if (lane == 0) { sums[2 * c] = s; sums[2 * c + 1] = ss; }
+  int c;
+  double s[2];
+  if (wave_channel_sums<2>(partial, nblk, C, c, s)) { sums[2 * c] = s[0]; sums[2 * c + 1] = s[1]; }
 }
 
 // per-wave partial rows of conv_wd16_kernel ([rows][2][C] floats) -> (sum, sum of squares) pairs in float64: a block walks its rows with
@@ -203,30 +268,21 @@ __global__ __launch_bounds__(256) void conv_stats_rows_kernel(const float* __res
   }
 }
 
-// ... and the backward finish from LOCAL sums (this rank's dgamma / dbeta: the gradient all-reduce adds the ranks) and GLOBAL
-// sums over `count` pixels of all ranks (the mean terms of the input gradient).
+// ... and the backward finish from the all-reduced [C][2] rows: LOCAL and GLOBAL sums as bn_bwd_coef takes them.
 __global__ __launch_bounds__(256) void bn_bwd_finish_sync_kernel(const double* __restrict__ local, const double* __restrict__ global,
                                                                  int C, double count, const float* __restrict__ gamma,
                                                                  const float* __restrict__ invstd, float* __restrict__ dgamma,
                                                                  float* __restrict__ dbeta, float* __restrict__ coef) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
-  dgamma[c] = (float)local[2 * c + 1];
-  dbeta[c] = (float)local[2 * c];
-  const double ka = (double)gamma[c] * (double)invstd[c];
-  coef[c] = (float)ka;
-  coef[C + c] = (float)(ka * global[2 * c] / count);
-  coef[2 * C + c] = (float)(ka * global[2 * c + 1] / count);
+  bn_bwd_coef(c, C, local[2 * c], local[2 * c + 1], global[2 * c], global[2 * c + 1], count, gamma, invstd, dgamma, dbeta, coef);
 }
 
 __global__ __launch_bounds__(256) void colsum_finish_kernel(const double* __restrict__ partial, int nblk, int C,
                                                             float* __restrict__ out) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (c >= C) return;
-  double s = 0;
-  for (int b = lane; b < nblk; b += 64) s += partial[(size_t)b * C + c];
-  s = wave_sum_d(s);
-  if (lane == 0) out[c] = (float)s;
+  int c;
+  double s[1];
+  if (wave_channel_sums<1>(partial, nblk, C, c, s)) out[c] = (float)s[0];
 }
 
 // dy <- dz in place (BatchNorm + ReLU backward), all per-channel constants precomputed.
@@ -247,38 +303,20 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(float* __restrict__ d
   const long long total = npix * C4;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
     const int cq = (int)(e & (C4 - 1));
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + 4 * cq);
-    const f32x4 sf = *reinterpret_cast<const f32x4*>(shift + 4 * cq);
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + 4 * cq);
-    const f32x4 is = *reinterpret_cast<const f32x4*>(invstd + 4 * cq);
-    const f32x4 ka = *reinterpret_cast<const f32x4*>(coef + 4 * cq);
-    const f32x4 kb = *reinterpret_cast<const f32x4*>(coef + C + 4 * cq);
-    const f32x4 kc = *reinterpret_cast<const f32x4*>(coef + 2 * C + 4 * cq);
+    const BnCh4 ch = bn_ld(scale, shift, mean, invstd, 4 * cq);
+    const BnCoef4 co = bn_coef_ld(coef, C, 4 * cq);
     f32x4 g;
     if (RANK1) {
       const float gp = dpred[e >> c4_shift];              // (C4 is a power of two: no 64-bit division per element)
-      const f32x4 wv = *reinterpret_cast<const f32x4*>(w1 + 4 * cq);
+      const f32x4 wv = ld4(w1 + 4 * cq);
 #pragma unroll
       for (int k = 0; k < 4; ++k) g[k] = gp * wv[k];
     } else {
       g = mfpa_ld_act4(dy, (size_t)e * 4, dy16);
     }
-    const f32x4 zz = mfpa_ld_act4(z, (size_t)e * 4, z16);
-    f32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float gg = (zz[k] * sc[k] + sf[k] > 0.f) ? g[k] : 0.f;
-      if (drop_thresh) gg = mfpa_keep(drop_seed, drop_thresh, (unsigned long long)e * 4 + k) ? gg * drop_scale : 0.f;
-      const float xh = (zz[k] - mu[k]) * is[k];
-      o[k] = ka[k] * gg - kb[k] - kc[k] * xh;
-    }
+    const f32x4 o = bn_dz4(g, mfpa_ld_act4(z, (size_t)e * 4, z16), ch, co, drop_seed, drop_thresh, drop_scale, (unsigned long long)e * 4);
     if (write_f32) *reinterpret_cast<f32x4*>(dy + e * 4) = o;   // (0: every consumer of dz reads the bf16 copy -- the plain-bf16 train step)
-    if (dz16) {                              // the bf16 copy the weight-gradient kernel reads (wgrad precision 3)
-      bf16x4 h;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) h[k] = (__bf16)o[k];
-      *reinterpret_cast<bf16x4*>(dz16 + e * 4) = h;
-    }
+    if (dz16) st_bf16x4(dz16 + e * 4, o);    // the bf16 copy the weight-gradient kernel reads (wgrad precision 3)
   }
 }
 
@@ -302,44 +340,31 @@ __global__ __launch_bounds__(256) void bn_bwd_apply8_kernel(float* __restrict__ 
       const float gp = dpred[e >> c8_shift];                // (C8 is a power of two: no 64-bit division per element)
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(w1 + c0 + 4 * h);
+        const f32x4 wv = ld4(w1 + c0 + 4 * h);
 #pragma unroll
         for (int k = 0; k < 4; ++k) g[h][k] = gp * wv[k];
       }
     } else {
-      g[0] = *reinterpret_cast<const f32x4*>(dy + e * 8);
-      g[1] = *reinterpret_cast<const f32x4*>(dy + e * 8 + 4);
+      g[0] = ld4(dy + e * 8);
+      g[1] = ld4(dy + e * 8 + 4);
     }
     const uint4 zr = *reinterpret_cast<const uint4*>(z16 + e * 8);
     const unsigned zu[4] = {zr.x, zr.y, zr.z, zr.w};
     f32x4 o[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + c0 + 4 * h), sf = *reinterpret_cast<const f32x4*>(shift + c0 + 4 * h);
-      const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c0 + 4 * h), is = *reinterpret_cast<const f32x4*>(invstd + c0 + 4 * h);
-      const f32x4 ka = *reinterpret_cast<const f32x4*>(coef + c0 + 4 * h), kb = *reinterpret_cast<const f32x4*>(coef + C + c0 + 4 * h);
-      const f32x4 kc = *reinterpret_cast<const f32x4*>(coef + 2 * C + c0 + 4 * h);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const unsigned u = zu[2 * h + (k >> 1)];
-        const float zz = __uint_as_float((k & 1) ? (u & 0xffff0000u) : (u << 16));
-        float gg = (zz * sc[k] + sf[k] > 0.f) ? g[h][k] : 0.f;
-        if (drop_thresh) gg = mfpa_keep(drop_seed, drop_thresh, (unsigned long long)e * 8 + 4 * h + k) ? gg * drop_scale : 0.f;
-        o[h][k] = ka[k] * gg - kb[k] - kc[k] * ((zz - mu[k]) * is[k]);
-      }
+      const f32x4 zz = {__uint_as_float(zu[2 * h] << 16), __uint_as_float(zu[2 * h] & 0xffff0000u), __uint_as_float(zu[2 * h + 1] << 16),
+                        __uint_as_float(zu[2 * h + 1] & 0xffff0000u)};
+      o[h] = bn_dz4(g[h], zz, bn_ld(scale, shift, mean, invstd, c0 + 4 * h), bn_coef_ld(coef, C, c0 + 4 * h), drop_seed, drop_thresh,
+                    drop_scale, (unsigned long long)e * 8 + 4 * h);
     }
     if (write_f32) {
       *reinterpret_cast<f32x4*>(dy + e * 8) = o[0];
       *reinterpret_cast<f32x4*>(dy + e * 8 + 4) = o[1];
     }
     if (dz16) {
-      bf16x4 h0, h1;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { h0[k] = (__bf16)o[0][k]; h1[k] = (__bf16)o[1][k]; }
-      uint4 pk;
-      const uint2 a = __builtin_bit_cast(uint2, h0), b = __builtin_bit_cast(uint2, h1);
-      pk.x = a.x; pk.y = a.y; pk.z = b.x; pk.w = b.y;
-      *reinterpret_cast<uint4*>(dz16 + e * 8) = pk;
+      const uint2 a = __builtin_bit_cast(uint2, to_bf16x4(o[0])), b = __builtin_bit_cast(uint2, to_bf16x4(o[1]));
+      *reinterpret_cast<uint4*>(dz16 + e * 8) = uint4{a.x, a.y, b.x, b.y};
     }
   }
 }
@@ -370,21 +395,16 @@ __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const float* __restri
         m[k] = y > m[k] ? y : m[k];
       }
     }
-    if (p16) {
-      bf16x4 h;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) h[k] = (__bf16)m[k];
-      *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(p) + e * 4) = h;
-    } else *reinterpret_cast<f32x4*>(p + e * 4) = m;
+    if (p16) st_bf16x4(reinterpret_cast<__bf16*>(p) + e * 4, m);
+    else *reinterpret_cast<f32x4*>(p + e * 4) = m;
   }
 }
 
 // dy_full += route(dp): the gradient of a pooled cell goes to the first maximum of its 2x2 window of
 // y = relu(z*scale+shift) (scan order (0,0),(0,1),(1,0),(1,1), strict >), as torch's max_pool2d backward.
 // SUMS: the pass also holds everything the BatchNorm backward of this very layer reduces next -- the finished dy and z of every pixel --
-// so it forms that reduction's per-channel partial sums {sum g, sum g * xhat} (g = dy * [z*scale+shift > 0] (* dropout), xhat =
-// (z - mean) * invstd: chan_reduce_kernel<1>'s terms) for its two rows, the odd last column and (last workgroup of a clip) the odd last
-// row included, and writes them as one row of `part` (rows x 2 x C float, the layout of the convolutions' stats_part, finished in
+// so it forms that reduction's per-channel partial sums {sum g, sum g * xhat} (bn_sums4: chan_reduce_kernel<1>'s terms) for its two rows, the
+// odd last column and (last workgroup of a clip) the odd last row included, and writes them as one row of `part` (st_part_row, finished in
 // float64 by mfpa_conv_stats_reduce): the separate reduction pass over dy and z (2.1 GB at the first level) is not run.
 // MODE 0: dy += route(dp); 1: ... and the BatchNorm-backward partial sums (SUMS); 2 (round 5): NOTHING of dy is written -- the pass forms
 // g = dy + route(dp) again and applies the BatchNorm + ReLU backward to it on the spot (coef = bn_bwd_finish_kernel's [3][C]), writing only the
@@ -402,44 +422,19 @@ __global__ __launch_bounds__(256) void maxpool_bwd_add_kernel(const float* __res
   constexpr bool SUMS = MODE == 1;
   const int Ho = H / 2, Wo = W / 2, C4 = C / 4;
   const int b = blockIdx.x / Ho, yo = blockIdx.x % Ho;     // one workgroup per pooled row: 32-bit index math only
-  // SUMS: 256 % C4 == 0 (checked by the launcher), so a thread meets ONE channel quad in all its trips: tid % C4
-  // (float64 like the chan_reduce_kernel<1> pass this replaces and like outconv_bwd_kernel<SUMS>: the two sums cancel heavily, and a float32
-  //  running sum over a row's ~500 pixels would put its rounding, relative to sum |g|, into dgamma / dbeta / dz of every engine precision)
+  // MODE >= 1: 256 % C4 == 0 (checked by the launcher), so a thread meets ONE channel quad in all its trips: tid % C4
   double s0[4] = {0., 0., 0., 0.}, s1[4] = {0., 0., 0., 0.};
-  f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = {0.f, 0.f, 0.f, 0.f}, scq = {0.f, 0.f, 0.f, 0.f}, sfq = {0.f, 0.f, 0.f, 0.f};
-  f32x4 ka = {0.f, 0.f, 0.f, 0.f}, kb = {0.f, 0.f, 0.f, 0.f}, kc = {0.f, 0.f, 0.f, 0.f};
+  BnCh4 ch = {};
+  BnCoef4 co = {};
   if (MODE >= 1) {
-    const int cqt = threadIdx.x % C4;
-    mu = *reinterpret_cast<const f32x4*>(mean + 4 * cqt);
-    is = *reinterpret_cast<const f32x4*>(invstd + 4 * cqt);
-    scq = *reinterpret_cast<const f32x4*>(scale + 4 * cqt);
-    sfq = *reinterpret_cast<const f32x4*>(shift + 4 * cqt);
-    if (MODE == 2) {
-      ka = *reinterpret_cast<const f32x4*>(coef + 4 * cqt);
-      kb = *reinterpret_cast<const f32x4*>(coef + C + 4 * cqt);
-      kc = *reinterpret_cast<const f32x4*>(coef + 2 * C + 4 * cqt);
-    }
+    ch = bn_ld(scale, shift, mean, invstd, 4 * (threadIdx.x % C4));
+    if (MODE == 2) co = bn_coef_ld(coef, C, 4 * (threadIdx.x % C4));
   }
-  // MODE 2: one pixel's four channels through the BatchNorm + ReLU (+ dropout) backward (bn_bwd_apply_kernel's formula), bf16 dz out
-  auto apply = [&](const f32x4& d, const f32x4& v, size_t elem0) {
-    bf16x4 h;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float gg = (v[k] * scq[k] + sfq[k] > 0.f) ? d[k] : 0.f;
-      if (drop_thresh) gg = mfpa_keep(drop_seed, drop_thresh, (unsigned long long)elem0 + k) ? gg * drop_scale : 0.f;
-      h[k] = (__bf16)(ka[k] * gg - kb[k] - kc[k] * ((v[k] - mu[k]) * is[k]));
-    }
-    *reinterpret_cast<bf16x4*>(dz16 + elem0) = h;
-  };
-  // one pixel's four channels into the sums (its finished gradient d, its z)
-  auto add = [&](const f32x4& d, const f32x4& v, size_t elem0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float g = (v[k] * scq[k] + sfq[k] > 0.f) ? d[k] : 0.f;
-      if (drop_thresh) g = mfpa_keep(drop_seed, drop_thresh, (unsigned long long)elem0 + k) ? g * drop_scale : 0.f;
-      s0[k] += (double)g;
-      s1[k] += (double)g * (double)((v[k] - mu[k]) * is[k]);
-    }
+  // one pixel's four channels (its finished gradient d, its z, its first element elem0): MODE 1 into the sums, MODE 2 through the
+  // BatchNorm + ReLU (+ dropout) backward, bf16 dz out
+  auto finish = [&](const f32x4& d, const f32x4& v, size_t elem0) {
+    if (SUMS) bn_sums4(s0, s1, d, v, ch, drop_seed, drop_thresh, drop_scale, elem0);
+    if (MODE == 2) st_bf16x4(dz16 + elem0, bn_dz4(d, v, ch, co, drop_seed, drop_thresh, drop_scale, elem0));
   };
   for (int e32 = threadIdx.x; e32 < Wo * C4; e32 += 256) {
     const int cq = e32 % C4, xo = e32 / C4;
@@ -473,8 +468,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_add_kernel(const float* __res
 #pragma unroll
       for (int k = 0; k < 4; ++k) cur[k] += (arg[k] == t) ? g[k] : 0.f;
       if (MODE != 2 && !nowrite) *reinterpret_cast<f32x4*>(dy + off) = cur;
-      if (SUMS) add(cur, vz[t], off);
-      if (MODE == 2) apply(cur, vz[t], off);
+      finish(cur, vz[t], off);
     }
   }
   if (MODE >= 1) {
@@ -482,39 +476,18 @@ __global__ __launch_bounds__(256) void maxpool_bwd_add_kernel(const float* __res
       for (int e32 = threadIdx.x; e32 < 2 * C4; e32 += 256) {
         const int cq = e32 % C4, r = e32 / C4;
         const size_t off = (((size_t)b * H + 2 * yo + r) * W + (W - 1)) * C + 4 * cq;
-        if (SUMS) add(mfpa_ld_act4(dy, off, d16), mfpa_ld_act4(z, off, z16), off);
-        else apply(mfpa_ld_act4(dy, off, d16), mfpa_ld_act4(z, off, z16), off);
+        finish(mfpa_ld_act4(dy, off, d16), mfpa_ld_act4(z, off, z16), off);
       }
     }
     if ((H & 1) && yo == Ho - 1) {                          // ... and so does the last row: the clip's last workgroup takes it
       for (int e32 = threadIdx.x; e32 < W * C4; e32 += 256) {
         const int cq = e32 % C4, x = e32 / C4;
         const size_t off = (((size_t)b * H + (H - 1)) * W + x) * C + 4 * cq;
-        if (SUMS) add(mfpa_ld_act4(dy, off, d16), mfpa_ld_act4(z, off, z16), off);
-        else apply(mfpa_ld_act4(dy, off, d16), mfpa_ld_act4(z, off, z16), off);
+        finish(mfpa_ld_act4(dy, off, d16), mfpa_ld_act4(z, off, z16), off);
       }
     }
   }
-  if (SUMS) {
-    __shared__ double red[256 * 8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      red[threadIdx.x * 8 + k] = s0[k];
-      red[threadIdx.x * 8 + 4 + k] = s1[k];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < C4) {                            // fixed order: deterministic
-      for (int r = 1; r < 256 / C4; ++r)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          s0[k] += red[(r * C4 + threadIdx.x) * 8 + k];
-          s1[k] += red[(r * C4 + threadIdx.x) * 8 + 4 + k];
-        }
-      float* row = part + (size_t)blockIdx.x * 2 * C;
-      *reinterpret_cast<f32x4*>(row + 4 * threadIdx.x) = f32x4{(float)s0[0], (float)s0[1], (float)s0[2], (float)s0[3]};
-      *reinterpret_cast<f32x4*>(row + C + 4 * threadIdx.x) = f32x4{(float)s1[0], (float)s1[1], (float)s1[2], (float)s1[3]};
-    }
-  }
+  if (SUMS && wg_pair_sums(s0, s1, C4, 256 / C4)) st_part_row(part, C, threadIdx.x, s0, s1);
 }
 
 // ------------------------------------------------------------------ OutConv (1x1 -> 1 class) in training
@@ -547,8 +520,8 @@ __global__ __launch_bounds__(256) void outconv_fwd_kernel(const float* __restric
 
 // dy[p][c] = dpred[p]*w[c];  partial[blk][c] = sum_p dpred[p]*y[p][c] (c < C), partial[blk][C] = sum_p dpred[p]
 // SUMS: dy is not written (the BatchNorm backward forms it again from dpred and w: bn_bwd_apply_kernel<RANK1>); instead the pass, which holds
-// z and dy of every element anyway, also forms the partial sums of that BatchNorm backward -- {sum g, sum g * xhat}, g = dy * [y > 0], xhat =
-// (z - mean) * invstd -- as one row of `part` (blocks x 2 x C float, the convolutions' stats_part layout) per workgroup.
+// z and dy of every element anyway, also forms the partial sums of that BatchNorm backward (bn_sums4; the OutConv's input carries no dropout:
+// threshold 0) as one row of `part` (blocks x 2 x C float, the convolutions' stats_part layout) per workgroup.
 template <bool SUMS>
 __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restrict__ z, const float* __restrict__ dpred,
                                                           long long npix, int C, const float* __restrict__ scale,
@@ -557,13 +530,13 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restric
                                                           const float* __restrict__ mean, const float* __restrict__ invstd,
                                                           float* __restrict__ part, int z16) {
   const int lpp = C / 4, sub = threadIdx.x % lpp, pl = threadIdx.x / lpp, ppb = 256 / lpp;
-  const f32x4 wv = *reinterpret_cast<const f32x4*>(w + 4 * sub);
-  const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + 4 * sub);
-  const f32x4 sf = *reinterpret_cast<const f32x4*>(shift + 4 * sub);
-  f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 wv = ld4(w + 4 * sub);
+  BnCh4 ch = {};
+  ch.scale = ld4(scale + 4 * sub);
+  ch.shift = ld4(shift + 4 * sub);
   if (SUMS) {
-    mu = *reinterpret_cast<const f32x4*>(mean + 4 * sub);
-    is = *reinterpret_cast<const f32x4*>(invstd + 4 * sub);
+    ch.mean = ld4(mean + 4 * sub);
+    ch.invstd = ld4(invstd + 4 * sub);
   }
   double sw[4] = {0, 0, 0, 0}, sb = 0, s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
   for (long long p = (long long)blockIdx.x * ppb + pl; p < npix; p += (long long)gridDim.x * ppb) {
@@ -572,38 +545,15 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restric
     f32x4 o;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float y = v[k] * sc[k] + sf[k];
+      const float y = v[k] * ch.scale[k] + ch.shift[k];
       sw[k] += (double)g * (double)(y > 0.f ? y : 0.f);
       o[k] = g * wv[k];
-      if (SUMS) {
-        const float gg = y > 0.f ? o[k] : 0.f;
-        s0[k] += (double)gg;
-        s1[k] += (double)gg * (double)((v[k] - mu[k]) * is[k]);
-      }
     }
-    if (!SUMS) *reinterpret_cast<f32x4*>(dy + (size_t)p * C + 4 * sub) = o;
+    if (SUMS) bn_sums4(s0, s1, o, v, ch, 0u, 0u, 1.f, 0ull);
+    else *reinterpret_cast<f32x4*>(dy + (size_t)p * C + 4 * sub) = o;
     if (sub == 0) sb += (double)g;
   }
-  if (SUMS) {
-    __shared__ double sh2[256 * 8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      sh2[threadIdx.x * 8 + k] = s0[k];
-      sh2[threadIdx.x * 8 + 4 + k] = s1[k];
-    }
-    __syncthreads();
-    if (pl == 0) {
-      for (int r = 1; r < ppb; ++r)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          s0[k] += sh2[(r * lpp + sub) * 8 + k];
-          s1[k] += sh2[(r * lpp + sub) * 8 + 4 + k];
-        }
-      float* row = part + (size_t)blockIdx.x * 2 * C;
-      *reinterpret_cast<f32x4*>(row + 4 * sub) = f32x4{(float)s0[0], (float)s0[1], (float)s0[2], (float)s0[3]};
-      *reinterpret_cast<f32x4*>(row + C + 4 * sub) = f32x4{(float)s1[0], (float)s1[1], (float)s1[2], (float)s1[3]};
-    }
-  }
+  if (SUMS && wg_pair_sums(s0, s1, lpp, ppb)) st_part_row(part, C, sub, s0, s1);
   __shared__ double sh[256 * 5];
 #pragma unroll
   for (int k = 0; k < 4; ++k) sh[threadIdx.x * 5 + k] = sw[k];
@@ -622,6 +572,18 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------ L1 loss (mean), float32 pred vs float64 target
+// sum of one float64 per thread over a 256-thread workgroup (LDS tree, fixed order); the result is thread 0's
+__device__ __forceinline__ double block_sum_d(double s) {
+  __shared__ double sh[256];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
 __global__ __launch_bounds__(256) void l1_kernel(const float* __restrict__ pred, const double* __restrict__ target,
                                                  long long n, float* __restrict__ dpred, double* __restrict__ partial) {
   double s = 0;
@@ -631,27 +593,15 @@ __global__ __launch_bounds__(256) void l1_kernel(const float* __restrict__ pred,
     s += fabs(d);
     if (dpred) dpred[i] = d > 0 ? inv : (d < 0 ? -inv : 0.f);
   }
-  __shared__ double sh[256];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+  s = block_sum_d(s);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 __global__ void l1_finish_kernel(const double* __restrict__ partial, int nblk, long long n, double* __restrict__ loss) {
-  __shared__ double sh[256];
   double s = 0;
   for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = sh[0] / (double)n;
+  s = block_sum_d(s);
+  if (threadIdx.x == 0) loss[0] = s / (double)n;
 }
 
 // ------------------------------------------------------------------ Adam (torch.optim.Adam, no weight decay, no amsgrad)
@@ -755,7 +705,6 @@ __global__ __launch_bounds__(256) void pack_conv_weights_batch_kernel(const mfpa
 __global__ __launch_bounds__(256) void act_to_bf16_kernel(const float* __restrict__ z, long long n4, int C, const float* __restrict__ scale,
                                                           const float* __restrict__ shift, unsigned drop_seed, unsigned drop_thresh,
                                                           float drop_scale, __bf16* __restrict__ out) {
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
     f32x4 v = *reinterpret_cast<const f32x4*>(z + 4 * i);
     if (scale) {
@@ -769,19 +718,48 @@ __global__ __launch_bounds__(256) void act_to_bf16_kernel(const float* __restric
         for (int k = 0; k < 4; ++k) v[k] = mfpa_keep(drop_seed, drop_thresh, (unsigned long long)(4 * i + k)) ? v[k] * drop_scale : 0.f;
       }
     }
-    bf16x4_t o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = (__bf16)v[k];
-    *reinterpret_cast<bf16x4_t*>(out + 4 * i) = o;
+    st_bf16x4(out + 4 * i, v);
   }
 }
 
-}  // namespace
+// ------------------------------------------------------------------ host side: shape predicates and launch sequences, each written once
+// chan_reduce_kernel's shapes: whole channel quads, and a block's 256 threads split evenly over them (or they over the threads)
+bool bn_shape_ok(long long npix, int C) {
+  return npix >= 0 && C >= 4 && C % 4 == 0 && !(C / 4 < 256 && 256 % (C / 4) != 0) && !(C / 4 > 256 && (C / 4) % 256 != 0);
+}
+// conv_stats_rows_kernel's: the same split with one channel per lane
+bool rows_shape_ok(int C) { return C >= 1 && !(C < 256 && 256 % C) && !(C > 256 && C % 256); }
+// the OutConv kernels': one pixel's C / 4 lanes are a power-of-two slice of a wavefront or of the block
+bool outconv_shape_ok(long long npix, int C) { return npix >= 0 && C >= 4 && C <= 256 && !(C & (C - 1)); }
+// the pool kernels': at least one window, whole channel quads, one workgroup per pooled row in a 32-bit grid
+bool pool_shape_ok(int B, int H, int W, int C) {
+  return B >= 0 && H >= 2 && W >= 2 && C >= 4 && C % 4 == 0 && (long long)B * (H / 2) <= 0x7fffffffLL;
+}
+
+// chan_reduce_kernel<MODE> over npix pixels into `workspace`; returns the number of block partials a finish kernel has to sum
+template <int MODE>
+int reduce_pixels(hipStream_t s, const float* x, const float* z, long long npix, int C, const float* scale, const float* shift,
+                  const float* mean, const float* invstd, double* workspace, unsigned drop_seed, unsigned drop_thresh, float drop_scale,
+                  int z16) {
+  const int rows = 256 / (C / 4 < 256 ? C / 4 : 256);
+  const int nblk = grid_for(npix, rows * 8, RED_BLOCKS);
+  hipLaunchKernelGGL(chan_reduce_kernel<MODE>, dim3(nblk), dim3(256), 0, s, x, z, npix, C, scale, shift, mean, invstd, workspace, drop_seed,
+                     drop_thresh, drop_scale, z16);
+  return nblk;
+}
+// conv_stats_rows_kernel over the rows of `part`, likewise
+int reduce_rows(hipStream_t s, const float* part, long long rows, int C, double* workspace) {
+  const int groups = 256 / (C < 256 ? C : 256);
+  const int nblk = grid_for(rows, groups * 8, RED_BLOCKS);
+  hipLaunchKernelGGL(conv_stats_rows_kernel, dim3(nblk), dim3(256), 0, s, part, rows, C, workspace);
+  return nblk;
+}
 
 template <bool RANK1>
-static void launch_bn_bwd_apply(hipStream_t s, float* dy, const float* z, long long npix, int C, const float* scale, const float* shift,
-                                const float* mean, const float* invstd, const float* coef, unsigned drop_seed, unsigned drop_thresh,
-                                float drop_scale, __bf16* dz16, int write_f32, const float* dpred, const float* w1, int z16, int dy16) {
+void launch_bn_bwd_apply(hipStream_t s, float* dy, const float* z, long long npix, int C, const float* scale, const float* shift,
+                         const float* mean, const float* invstd, const float* coef, unsigned drop_seed, unsigned drop_thresh,
+                         float drop_scale, void* dz_bf16, int write_f32, const float* dpred, const float* w1, int z16, int dy16) {
+  __bf16* dz16 = reinterpret_cast<__bf16*>(dz_bf16);
   if (z16 && !dy16 && C % 8 == 0)
     hipLaunchKernelGGL(bn_bwd_apply8_kernel<RANK1>, dim3(grid_for(npix * (C / 8))), dim3(256), 0, s, dy, reinterpret_cast<const unsigned short*>(z),
                        npix, C, scale, shift, mean, invstd, coef, drop_seed, drop_thresh, drop_scale, dz16, write_f32, dpred, w1);
@@ -789,6 +767,65 @@ static void launch_bn_bwd_apply(hipStream_t s, float* dy, const float* z, long l
     hipLaunchKernelGGL(bn_bwd_apply_kernel<RANK1>, dim3(grid_for(npix * (C / 4))), dim3(256), 0, s, dy, z, npix, C, scale, shift, mean, invstd,
                        coef, drop_seed, drop_thresh, drop_scale, dz16, write_f32, dpred, w1, z16, dy16);
 }
+
+// The single-GPU BatchNorm + ReLU backward from block partials already in `workspace`: dgamma / dbeta / coefficients, then the apply pass
+int bn_bwd_finish_apply_local(hipStream_t s, int nblk, float* dy, const float* z, long long npix, int C, const float* gamma, const float* scale,
+                              const float* shift, const float* mean, const float* invstd, float* dgamma, float* dbeta, float* coef,
+                              double* workspace, unsigned drop_seed, unsigned drop_thresh, float drop_scale, void* dz_bf16, int write_f32,
+                              int z16, int dy16) {
+  hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, s, workspace, nblk, C, (double)npix, gamma, invstd, dgamma,
+                     dbeta, coef);
+  MFPA_CHECK_LAUNCH();
+  launch_bn_bwd_apply<false>(s, dy, z, npix, C, scale, shift, mean, invstd, coef, drop_seed, drop_thresh, drop_scale, dz_bf16, write_f32,
+                             nullptr, nullptr, z16, dy16);
+  MFPA_CHECK_LAUNCH();
+  return MFPA_OK;
+}
+
+// mfpa_bn_relu_bwd_finish and ..._finish_rank1 after their argument checks: coefficients from the (all-reduced) sums, then the apply pass
+template <bool RANK1>
+int bn_bwd_finish_apply(hipStream_t s, float* dy, const float* z, long long npix, int C, const float* gamma, const float* scale,
+                        const float* shift, const float* mean, const float* invstd, const double* local_sums, const double* global_sums,
+                        double global_count, float* dgamma, float* dbeta, float* coef, unsigned drop_seed, unsigned drop_thresh,
+                        float drop_scale, void* dz_bf16, int write_f32, const float* dpred, const float* w1, int z16, int dy16) {
+  hipLaunchKernelGGL(bn_bwd_finish_sync_kernel, dim3((C + 255) / 256), dim3(256), 0, s, local_sums, global_sums, C, global_count,
+                     gamma, invstd, dgamma, dbeta, coef);
+  MFPA_CHECK_LAUNCH();
+  if (npix == 0) return MFPA_OK;
+  launch_bn_bwd_apply<RANK1>(s, dy, z, npix, C, scale, shift, mean, invstd, coef, drop_seed, drop_thresh, drop_scale, dz_bf16, write_f32,
+                             dpred, w1, z16, dy16);
+  MFPA_CHECK_LAUNCH();
+  return MFPA_OK;
+}
+
+int outconv_bwd_blocks(long long npix, int C) { return grid_for(npix, (256 / (C / 4)) * 16, RED_BLOCKS); }
+
+// mfpa_outconv_bwd (dy written) and ..._sums (the BatchNorm-backward row partials instead) after their argument checks
+template <bool SUMS>
+int outconv_bwd(hipStream_t s, const float* z, const float* dpred, long long npix, int C, const float* scale, const float* shift,
+                const float* mean, const float* invstd, const float* w, float* dy, float* dwb, double* workspace, float* part, int z16) {
+  const int nblk = outconv_bwd_blocks(npix, C);
+  hipLaunchKernelGGL(outconv_bwd_kernel<SUMS>, dim3(nblk), dim3(256), 0, s, z, dpred, npix, C, scale, shift, w, dy, workspace, mean, invstd,
+                     part, z16);
+  MFPA_CHECK_LAUNCH();
+  // finish: column sums of the (nblk, C+1) partial matrix: C weight gradients then the bias gradient
+  hipLaunchKernelGGL(colsum_finish_kernel, dim3((C + 1 + 3) / 4), dim3(256), 0, s, workspace, nblk, C + 1, dwb);
+  MFPA_CHECK_LAUNCH();
+  return MFPA_OK;
+}
+
+// one maxpool_bwd_add_kernel<MODE> launch: one workgroup per pooled row
+template <int MODE>
+int pool_bwd(hipStream_t s, const float* z, int B, int H, int W, int C, const float* scale, const float* shift, const float* mean,
+             const float* invstd, const float* dp, float* dy, unsigned drop_seed, unsigned drop_thresh, float drop_scale, float* part, int z16,
+             int d16, int nowrite, const float* coef, void* dz_bf16) {
+  hipLaunchKernelGGL(maxpool_bwd_add_kernel<MODE>, dim3((unsigned)(B * (H / 2))), dim3(256), 0, s, z, B, H, W, C, scale, shift, dp, dy,
+                     drop_seed, drop_thresh, drop_scale, mean, invstd, part, z16, d16, nowrite, coef, reinterpret_cast<__bf16*>(dz_bf16));
+  MFPA_CHECK_LAUNCH();
+  return MFPA_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -799,12 +836,9 @@ int mfpa_bn_stats(const float* z, long long npix, int C, const float* gamma, con
                   float* running_var, double* workspace, int z_is_bf16, void* stream) {
   if (npix == 0) return MFPA_OK;
   if (!z || !gamma || !beta || !mean || !invstd || !scale || !shift || !workspace) return MFPA_EINVAL;
-  if (npix < 0 || C < 4 || C % 4 || (C / 4 < 256 && 256 % (C / 4) != 0) || (C / 4 > 256 && (C / 4) % 256 != 0)) return MFPA_EINVAL;
+  if (!bn_shape_ok(npix, C)) return MFPA_EINVAL;
   hipStream_t s = mfpa_stream(stream);
-  const int rows = 256 / (C / 4 < 256 ? C / 4 : 256);
-  const int nblk = grid_for(npix, rows * 8, RED_BLOCKS);
-  hipLaunchKernelGGL(chan_reduce_kernel<0>, dim3(nblk), dim3(256), 0, s, z, nullptr, npix, C, nullptr, nullptr,
-                     nullptr, nullptr, workspace, 0u, 0u, 1.f, z_is_bf16);
+  const int nblk = reduce_pixels<0>(s, z, nullptr, npix, C, nullptr, nullptr, nullptr, nullptr, workspace, 0u, 0u, 1.f, z_is_bf16);
   MFPA_CHECK_LAUNCH();
   hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, s, workspace, nblk, C, (double)npix,
                      eps, momentum, gamma, beta, mean, invstd, scale, shift, running_mean, running_var);
@@ -820,35 +854,19 @@ int mfpa_bn_relu_bwd(float* dy, const float* z, long long npix, int C, const flo
   if (!write_f32 && !dz_bf16) return MFPA_EINVAL;
   if (!dy || !z || !gamma || !scale || !shift || !mean || !invstd || !dgamma || !dbeta || !coef || !workspace) return MFPA_EINVAL;
   if (C & (C - 1)) return MFPA_EINVAL;   // channel counts of this UNet are powers of two (64 ... 1024)
-  if (npix < 0 || C < 4 || C % 4 || (C / 4 < 256 && 256 % (C / 4) != 0) || (C / 4 > 256 && (C / 4) % 256 != 0)) return MFPA_EINVAL;
+  if (!bn_shape_ok(npix, C)) return MFPA_EINVAL;
   hipStream_t s = mfpa_stream(stream);
-  const int rows = 256 / (C / 4 < 256 ? C / 4 : 256);
-  const int nblk = grid_for(npix, rows * 8, RED_BLOCKS);
-  hipLaunchKernelGGL(chan_reduce_kernel<1>, dim3(nblk), dim3(256), 0, s, dy, z, npix, C, scale, shift, mean, invstd,
-                     workspace, drop_seed, drop_thresh, drop_scale, z_is_bf16);
+  const int nblk = reduce_pixels<1>(s, dy, z, npix, C, scale, shift, mean, invstd, workspace, drop_seed, drop_thresh, drop_scale, z_is_bf16);
   MFPA_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, s, workspace, nblk, C, (double)npix,
-                     gamma, invstd, dgamma, dbeta, coef);
-  MFPA_CHECK_LAUNCH();
-  launch_bn_bwd_apply<false>(s, dy, z, npix, C, scale, shift,
-                     mean, invstd, coef, drop_seed, drop_thresh, drop_scale, reinterpret_cast<__bf16*>(dz_bf16), write_f32,
-                     (const float*)nullptr, (const float*)nullptr, z_is_bf16, 0);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
-}
-
-static bool bn_shape_ok(long long npix, int C) {
-  return npix >= 0 && C >= 4 && C % 4 == 0 && !(C / 4 < 256 && 256 % (C / 4) != 0) && !(C / 4 > 256 && (C / 4) % 256 != 0);
+  return bn_bwd_finish_apply_local(s, nblk, dy, z, npix, C, gamma, scale, shift, mean, invstd, dgamma, dbeta, coef, workspace, drop_seed,
+                                   drop_thresh, drop_scale, dz_bf16, write_f32, z_is_bf16, 0);
 }
 
 int mfpa_bn_stats_sums(const float* z, long long npix, int C, double* sums, double* workspace, int z_is_bf16, void* stream) {
   if (!sums || !workspace || !bn_shape_ok(npix, C) || (npix > 0 && !z)) return MFPA_EINVAL;
   hipStream_t s = mfpa_stream(stream);
   if (npix == 0) { MFPA_HIP(hipMemsetAsync(sums, 0, sizeof(double) * 2 * C, s)); return MFPA_OK; }
-  const int rows = 256 / (C / 4 < 256 ? C / 4 : 256);
-  const int nblk = grid_for(npix, rows * 8, RED_BLOCKS);
-  hipLaunchKernelGGL(chan_reduce_kernel<0>, dim3(nblk), dim3(256), 0, s, z, nullptr, npix, C, nullptr, nullptr,
-                     nullptr, nullptr, workspace, 0u, 0u, 1.f, z_is_bf16);
+  const int nblk = reduce_pixels<0>(s, z, nullptr, npix, C, nullptr, nullptr, nullptr, nullptr, workspace, 0u, 0u, 1.f, z_is_bf16);
   MFPA_CHECK_LAUNCH();
   hipLaunchKernelGGL(pair_sums_kernel, dim3((C + 3) / 4), dim3(256), 0, s, workspace, nblk, C, sums);
   MFPA_CHECK_LAUNCH();
@@ -856,11 +874,9 @@ int mfpa_bn_stats_sums(const float* z, long long npix, int C, double* sums, doub
 }
 
 int mfpa_conv_stats_reduce(const float* part, long long rows, int C, double* sums, double* workspace, void* stream) {
-  if (!part || !sums || !workspace || rows < 1 || C < 1 || (C < 256 && 256 % C) || (C > 256 && C % 256)) return MFPA_EINVAL;
+  if (!part || !sums || !workspace || rows < 1 || !rows_shape_ok(C)) return MFPA_EINVAL;
   hipStream_t s = mfpa_stream(stream);
-  const int groups = 256 / (C < 256 ? C : 256);
-  const int nblk = grid_for(rows, groups * 8, RED_BLOCKS);
-  hipLaunchKernelGGL(conv_stats_rows_kernel, dim3(nblk), dim3(256), 0, s, part, rows, C, workspace);
+  const int nblk = reduce_rows(s, part, rows, C, workspace);
   MFPA_CHECK_LAUNCH();
   hipLaunchKernelGGL(pair_sums_kernel, dim3((C + 3) / 4), dim3(256), 0, s, workspace, nblk, C, sums);
   MFPA_CHECK_LAUNCH();
@@ -872,12 +888,10 @@ int mfpa_conv_stats_reduce(const float* part, long long rows, int C, double* sum
 int mfpa_conv_stats_bn_finish(const float* part, long long rows, int C, double count, const float* gamma, const float* beta, float eps,
                               float momentum, float* mean, float* invstd, float* scale, float* shift, float* running_mean,
                               float* running_var, double* workspace, void* stream) {
-  if (!part || !workspace || rows < 1 || C < 1 || (C < 256 && 256 % C) || (C > 256 && C % 256)) return MFPA_EINVAL;
+  if (!part || !workspace || rows < 1 || !rows_shape_ok(C)) return MFPA_EINVAL;
   if (!gamma || !beta || !mean || !invstd || !scale || !shift || !(count >= 1.0)) return MFPA_EINVAL;
   hipStream_t s = mfpa_stream(stream);
-  const int groups = 256 / (C < 256 ? C : 256);
-  const int nblk = grid_for(rows, groups * 8, RED_BLOCKS);
-  hipLaunchKernelGGL(conv_stats_rows_kernel, dim3(nblk), dim3(256), 0, s, part, rows, C, workspace);
+  const int nblk = reduce_rows(s, part, rows, C, workspace);
   MFPA_CHECK_LAUNCH();
   hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, s, workspace, nblk, C, count, eps,
                      momentum, gamma, beta, mean, invstd, scale, shift, running_mean, running_var);
@@ -895,20 +909,12 @@ int mfpa_bn_relu_bwd_from_part(float* dy, const float* z, long long npix, int C,
   if (!gamma || !scale || !shift || !mean || !invstd || !part || !dgamma || !dbeta || !coef || !workspace || rows < 1) return MFPA_EINVAL;
   if (!write_f32 && !dz_bf16) return MFPA_EINVAL;
   if (dy_is_bf16 && write_f32) return MFPA_EINVAL;
-  if (npix < 1 || !bn_shape_ok(npix, C) || (C & (C - 1)) || !dy || !z || (C < 256 && 256 % C) || (C > 256 && C % 256)) return MFPA_EINVAL;
+  if (npix < 1 || !bn_shape_ok(npix, C) || (C & (C - 1)) || !dy || !z || !rows_shape_ok(C)) return MFPA_EINVAL;
   hipStream_t s = mfpa_stream(stream);
-  const int groups = 256 / (C < 256 ? C : 256);
-  const int nblk = grid_for(rows, groups * 8, RED_BLOCKS);
-  hipLaunchKernelGGL(conv_stats_rows_kernel, dim3(nblk), dim3(256), 0, s, part, rows, C, workspace);
+  const int nblk = reduce_rows(s, part, rows, C, workspace);
   MFPA_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, s, workspace, nblk, C, (double)npix, gamma, invstd, dgamma,
-                     dbeta, coef);
-  MFPA_CHECK_LAUNCH();
-  launch_bn_bwd_apply<false>(s, dy, z, npix, C, scale, shift,
-                     mean, invstd, coef, drop_seed, drop_thresh, drop_scale, reinterpret_cast<__bf16*>(dz_bf16), write_f32,
-                     (const float*)nullptr, (const float*)nullptr, z_is_bf16, dy_is_bf16);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
+  return bn_bwd_finish_apply_local(s, nblk, dy, z, npix, C, gamma, scale, shift, mean, invstd, dgamma, dbeta, coef, workspace, drop_seed,
+                                   drop_thresh, drop_scale, dz_bf16, write_f32, z_is_bf16, dy_is_bf16);
 }
 
 int mfpa_bn_stats_finish(const double* sums, double count, int C, const float* gamma, const float* beta, float eps,
@@ -928,10 +934,7 @@ int mfpa_bn_relu_bwd_sums(const float* dy, const float* z, long long npix, int C
   if (npix > 0 && (!dy || !z)) return MFPA_EINVAL;
   hipStream_t s = mfpa_stream(stream);
   if (npix == 0) { MFPA_HIP(hipMemsetAsync(sums, 0, sizeof(double) * 2 * C, s)); return MFPA_OK; }
-  const int rows = 256 / (C / 4 < 256 ? C / 4 : 256);
-  const int nblk = grid_for(npix, rows * 8, RED_BLOCKS);
-  hipLaunchKernelGGL(chan_reduce_kernel<1>, dim3(nblk), dim3(256), 0, s, dy, z, npix, C, scale, shift, mean, invstd,
-                     workspace, drop_seed, drop_thresh, drop_scale, z_is_bf16);
+  const int nblk = reduce_pixels<1>(s, dy, z, npix, C, scale, shift, mean, invstd, workspace, drop_seed, drop_thresh, drop_scale, z_is_bf16);
   MFPA_CHECK_LAUNCH();
   hipLaunchKernelGGL(pair_sums_kernel, dim3((C + 3) / 4), dim3(256), 0, s, workspace, nblk, C, sums);
   MFPA_CHECK_LAUNCH();
@@ -946,16 +949,9 @@ int mfpa_bn_relu_bwd_finish(float* dy, const float* z, long long npix, int C, co
   if (!write_f32 && !dz_bf16) return MFPA_EINVAL;
   if (dy_is_bf16 && write_f32) return MFPA_EINVAL;                    // a bfloat16 dy cannot take the float32 dz in place
   if (!bn_shape_ok(npix, C) || (C & (C - 1)) || !(global_count >= 1.0) || (npix > 0 && (!dy || !z))) return MFPA_EINVAL;
-  hipStream_t s = mfpa_stream(stream);
-  hipLaunchKernelGGL(bn_bwd_finish_sync_kernel, dim3((C + 255) / 256), dim3(256), 0, s, local_sums, global_sums, C, global_count,
-                     gamma, invstd, dgamma, dbeta, coef);
-  MFPA_CHECK_LAUNCH();
-  if (npix == 0) return MFPA_OK;
-  launch_bn_bwd_apply<false>(s, dy, z, npix, C, scale, shift,
-                     mean, invstd, coef, drop_seed, drop_thresh, drop_scale, reinterpret_cast<__bf16*>(dz_bf16), write_f32,
-                     (const float*)nullptr, (const float*)nullptr, z_is_bf16, dy_is_bf16);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
+  return bn_bwd_finish_apply<false>(mfpa_stream(stream), dy, z, npix, C, gamma, scale, shift, mean, invstd, local_sums, global_sums,
+                                    global_count, dgamma, dbeta, coef, drop_seed, drop_thresh, drop_scale, dz_bf16, write_f32, nullptr,
+                                    nullptr, z_is_bf16, dy_is_bf16);
 }
 
 int mfpa_bn_relu_bwd_finish_rank1(const float* dpred, const float* w1, const float* z, long long npix, int C, const float* gamma,
@@ -965,25 +961,15 @@ int mfpa_bn_relu_bwd_finish_rank1(const float* dpred, const float* w1, const flo
   if (!dpred || !w1 || !gamma || !scale || !shift || !mean || !invstd || !local_sums || !global_sums || !dgamma || !dbeta || !coef) return MFPA_EINVAL;
   if (!dz_f32 && !dz_bf16) return MFPA_EINVAL;
   if (!bn_shape_ok(npix, C) || (C & (C - 1)) || !(global_count >= 1.0) || (npix > 0 && !z)) return MFPA_EINVAL;
-  hipStream_t s = mfpa_stream(stream);
-  hipLaunchKernelGGL(bn_bwd_finish_sync_kernel, dim3((C + 255) / 256), dim3(256), 0, s, local_sums, global_sums, C, global_count,
-                     gamma, invstd, dgamma, dbeta, coef);
-  MFPA_CHECK_LAUNCH();
-  if (npix == 0) return MFPA_OK;
-  launch_bn_bwd_apply<true>(s, dz_f32, z, npix, C, scale, shift,
-                     mean, invstd, coef, 0u, 0u, 1.f, reinterpret_cast<__bf16*>(dz_bf16), dz_f32 != nullptr ? 1 : 0, dpred, w1, z_is_bf16, 0);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
+  return bn_bwd_finish_apply<true>(mfpa_stream(stream), dz_f32, z, npix, C, gamma, scale, shift, mean, invstd, local_sums, global_sums,
+                                   global_count, dgamma, dbeta, coef, 0u, 0u, 1.f, dz_bf16, dz_f32 != nullptr ? 1 : 0, dpred, w1, z_is_bf16, 0);
 }
 
 int mfpa_colsum(const float* x, long long npix, int C, float* out, double* workspace, void* stream) {
   if (npix == 0) return MFPA_OK;
-  if (!x || !out || !workspace || npix < 0 || C < 4 || C % 4 || (C / 4 < 256 && 256 % (C / 4) != 0) || (C / 4 > 256 && (C / 4) % 256 != 0)) return MFPA_EINVAL;
+  if (!x || !out || !workspace || !bn_shape_ok(npix, C)) return MFPA_EINVAL;
   hipStream_t s = mfpa_stream(stream);
-  const int rows = 256 / (C / 4 < 256 ? C / 4 : 256);
-  const int nblk = grid_for(npix, rows * 8, RED_BLOCKS);
-  hipLaunchKernelGGL(chan_reduce_kernel<2>, dim3(nblk), dim3(256), 0, s, x, nullptr, npix, C, nullptr, nullptr, nullptr,
-                     nullptr, workspace, 0u, 0u, 1.f, 0);
+  const int nblk = reduce_pixels<2>(s, x, nullptr, npix, C, nullptr, nullptr, nullptr, nullptr, workspace, 0u, 0u, 1.f, 0);
   MFPA_CHECK_LAUNCH();
   hipLaunchKernelGGL(colsum_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, s, workspace, nblk, C, out);
   MFPA_CHECK_LAUNCH();
@@ -993,8 +979,7 @@ int mfpa_colsum(const float* x, long long npix, int C, float* out, double* works
 int mfpa_bn_relu_pool(const float* z, int B, int H, int W, int C, const float* scale, const float* shift, float* p,
                       unsigned drop_seed, unsigned drop_thresh, float drop_scale, int z_is_bf16, int p_is_bf16, void* stream) {
   if (B == 0) return MFPA_OK;
-  if (!z || !scale || !shift || !p || B < 0 || H < 2 || W < 2 || C < 4 || C % 4) return MFPA_EINVAL;
-  if ((long long)B * (H / 2) > 0x7fffffffLL) return MFPA_EINVAL;
+  if (!z || !scale || !shift || !p || !pool_shape_ok(B, H, W, C)) return MFPA_EINVAL;
   hipLaunchKernelGGL(bn_relu_pool_kernel, dim3((unsigned)(B * (H / 2))), dim3(256), 0, mfpa_stream(stream), z, B, H, W, C, scale,
                      shift, p, drop_seed, drop_thresh, drop_scale, z_is_bf16, p_is_bf16);
   MFPA_CHECK_LAUNCH();
@@ -1005,25 +990,19 @@ int mfpa_maxpool2_bwd_add(const float* z, int B, int H, int W, int C, const floa
                           const float* dp, float* dy, unsigned drop_seed, unsigned drop_thresh, float drop_scale,
                           int z_is_bf16, void* stream) {
   if (B == 0) return MFPA_OK;
-  if (!z || !scale || !shift || !dp || !dy || B < 0 || H < 2 || W < 2 || C < 4 || C % 4) return MFPA_EINVAL;
-  if ((long long)B * (H / 2) > 0x7fffffffLL) return MFPA_EINVAL;
-  hipLaunchKernelGGL(maxpool_bwd_add_kernel<0>, dim3((unsigned)(B * (H / 2))), dim3(256), 0, mfpa_stream(stream), z, B, H, W, C,
-                     scale, shift, dp, dy, drop_seed, drop_thresh, drop_scale, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, z_is_bf16,
-                     0, 0, (const float*)nullptr, (__bf16*)nullptr);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
+  if (!z || !scale || !shift || !dp || !dy || !pool_shape_ok(B, H, W, C)) return MFPA_EINVAL;
+  return pool_bwd<0>(mfpa_stream(stream), z, B, H, W, C, scale, shift, nullptr, nullptr, dp, dy, drop_seed, drop_thresh, drop_scale, nullptr,
+                     z_is_bf16, 0, 0, nullptr, nullptr);
 }
 
 int mfpa_maxpool2_bwd_add_sums(const float* z, int B, int H, int W, int C, const float* scale, const float* shift, const float* mean,
                                const float* invstd, const float* dp, float* dy, unsigned drop_seed, unsigned drop_thresh,
                                float drop_scale, float* part, int z_is_bf16, void* stream) {
   if (B == 0) return MFPA_OK;
-  if (!z || !scale || !shift || !mean || !invstd || !dp || !dy || !part || B < 0 || H < 2 || W < 2 || C < 4 || C % 4) return MFPA_EINVAL;
-  if ((long long)B * (H / 2) > 0x7fffffffLL || C / 4 > 256 || 256 % (C / 4)) return MFPA_EINVAL;   // a thread keeps ONE channel quad's sums
-  hipLaunchKernelGGL(maxpool_bwd_add_kernel<1>, dim3((unsigned)(B * (H / 2))), dim3(256), 0, mfpa_stream(stream), z, B, H, W, C,
-                     scale, shift, dp, dy, drop_seed, drop_thresh, drop_scale, mean, invstd, part, z_is_bf16, 0, 0, (const float*)nullptr, (__bf16*)nullptr);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
+  if (!z || !scale || !shift || !mean || !invstd || !dp || !dy || !part || !pool_shape_ok(B, H, W, C)) return MFPA_EINVAL;
+  if (C / 4 > 256 || 256 % (C / 4)) return MFPA_EINVAL;   // a thread keeps ONE channel quad's sums
+  return pool_bwd<1>(mfpa_stream(stream), z, B, H, W, C, scale, shift, mean, invstd, dp, dy, drop_seed, drop_thresh, drop_scale, part,
+                     z_is_bf16, 0, 0, nullptr, nullptr);
 }
 
 // An encoder block's last BatchNorm + ReLU backward WITHOUT its finished input gradient in memory (round 5): dy = the skip path's gradient
@@ -1037,26 +1016,20 @@ int mfpa_maxpool2_bwd_bn_relu_bwd(const float* z, int B, int H, int W, int C, co
                                   double* workspace, void* dz_bf16, int z_is_bf16, void* stream) {
   if (B == 0) return MFPA_OK;
   if (!z || !gamma || !scale || !shift || !mean || !invstd || !dp || !dy || !part || !dgamma || !dbeta || !coef || !workspace || !dz_bf16) return MFPA_EINVAL;
-  if (B < 0 || H < 2 || W < 2 || C < 4 || C % 4 || (C & (C - 1))) return MFPA_EINVAL;
-  if ((long long)B * (H / 2) > 0x7fffffffLL || C / 4 > 256 || 256 % (C / 4) || (C < 256 && 256 % C)) return MFPA_EINVAL;
+  if (!pool_shape_ok(B, H, W, C) || (C & (C - 1))) return MFPA_EINVAL;
+  if (C / 4 > 256 || 256 % (C / 4) || !rows_shape_ok(C)) return MFPA_EINVAL;
   hipStream_t s = mfpa_stream(stream);
-  const unsigned grid = (unsigned)(B * (H / 2));
   float* dyf = const_cast<float*>(reinterpret_cast<const float*>(dy));
-  hipLaunchKernelGGL(maxpool_bwd_add_kernel<1>, dim3(grid), dim3(256), 0, s, z, B, H, W, C, scale, shift, dp, dyf, drop_seed, drop_thresh,
-                     drop_scale, mean, invstd, part, z_is_bf16, dy_is_bf16, 1, (const float*)nullptr, (__bf16*)nullptr);
-  MFPA_CHECK_LAUNCH();
-  const long long rows = (long long)grid;
-  const int groups = 256 / (C < 256 ? C : 256);
-  const int nblk = grid_for(rows, groups * 8, RED_BLOCKS);
-  hipLaunchKernelGGL(conv_stats_rows_kernel, dim3(nblk), dim3(256), 0, s, part, rows, C, workspace);
+  int rc = pool_bwd<1>(s, z, B, H, W, C, scale, shift, mean, invstd, dp, dyf, drop_seed, drop_thresh, drop_scale, part, z_is_bf16, dy_is_bf16,
+                       1, nullptr, nullptr);
+  if (rc != MFPA_OK) return rc;
+  const int nblk = reduce_rows(s, part, (long long)B * (H / 2), C, workspace);
   MFPA_CHECK_LAUNCH();
   hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, s, workspace, nblk, C, (double)((long long)B * H * W), gamma, invstd,
                      dgamma, dbeta, coef);
   MFPA_CHECK_LAUNCH();
-  hipLaunchKernelGGL(maxpool_bwd_add_kernel<2>, dim3(grid), dim3(256), 0, s, z, B, H, W, C, scale, shift, dp, dyf, drop_seed, drop_thresh,
-                     drop_scale, mean, invstd, (float*)nullptr, z_is_bf16, dy_is_bf16, 1, coef, reinterpret_cast<__bf16*>(dz_bf16));
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
+  return pool_bwd<2>(s, z, B, H, W, C, scale, shift, mean, invstd, dp, dyf, drop_seed, drop_thresh, drop_scale, nullptr, z_is_bf16, dy_is_bf16,
+                     1, coef, dz_bf16);
 }
 
 int mfpa_act_to_bf16(const float* z, long long n, int C, const float* scale, const float* shift, unsigned drop_seed,
@@ -1073,7 +1046,7 @@ int mfpa_act_to_bf16(const float* z, long long n, int C, const float* scale, con
 int mfpa_outconv_fwd(const float* z, long long npix, int C, const float* scale, const float* shift, const float* w,
                      const float* bias, float* pred, int z_is_bf16, void* stream) {
   if (npix == 0) return MFPA_OK;
-  if (!z || !scale || !shift || !w || !bias || !pred || npix < 0 || C < 4 || C > 256 || (C & (C - 1))) return MFPA_EINVAL;
+  if (!z || !scale || !shift || !w || !bias || !pred || !outconv_shape_ok(npix, C)) return MFPA_EINVAL;
   hipLaunchKernelGGL(outconv_fwd_kernel, dim3(grid_for(npix, 256 / (C / 4), 256 * 32)), dim3(256), 0,
                      mfpa_stream(stream), z, npix, C, scale, shift, w, bias, pred, z_is_bf16);
   MFPA_CHECK_LAUNCH();
@@ -1084,21 +1057,13 @@ int mfpa_outconv_bwd(const float* z, const float* dpred, long long npix, int C, 
                      const float* w, float* dy, float* dwb, double* workspace, int z_is_bf16, void* stream) {
   if (npix == 0) return MFPA_OK;
   if (!z || !dpred || !scale || !shift || !w || !dy || !dwb || !workspace) return MFPA_EINVAL;
-  if (npix < 0 || C < 4 || C > 256 || (C & (C - 1))) return MFPA_EINVAL;
-  hipStream_t s = mfpa_stream(stream);
-  const int nblk = grid_for(npix, (256 / (C / 4)) * 16, RED_BLOCKS);
-  hipLaunchKernelGGL(outconv_bwd_kernel<false>, dim3(nblk), dim3(256), 0, s, z, dpred, npix, C, scale, shift, w, dy, workspace,
-                     (const float*)nullptr, (const float*)nullptr, (float*)nullptr, z_is_bf16);
-  MFPA_CHECK_LAUNCH();
-  // finish: column sums of the (nblk, C+1) partial matrix: C weight gradients then the bias gradient
-  hipLaunchKernelGGL(colsum_finish_kernel, dim3((C + 1 + 3) / 4), dim3(256), 0, s, workspace, nblk, C + 1, dwb);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
+  if (!outconv_shape_ok(npix, C)) return MFPA_EINVAL;
+  return outconv_bwd<false>(mfpa_stream(stream), z, dpred, npix, C, scale, shift, nullptr, nullptr, w, dy, dwb, workspace, nullptr, z_is_bf16);
 }
 
 int mfpa_outconv_bwd_rows(long long npix, int C, int* rows) {
-  if (!rows || npix < 0 || C < 4 || C > 256 || (C & (C - 1))) return MFPA_EINVAL;
-  *rows = npix == 0 ? 0 : grid_for(npix, (256 / (C / 4)) * 16, RED_BLOCKS);
+  if (!rows || !outconv_shape_ok(npix, C)) return MFPA_EINVAL;
+  *rows = npix == 0 ? 0 : outconv_bwd_blocks(npix, C);
   return MFPA_OK;
 }
 
@@ -1107,15 +1072,8 @@ int mfpa_outconv_bwd_sums(const float* z, const float* dpred, long long npix, in
                           int z_is_bf16, void* stream) {
   if (npix == 0) return MFPA_OK;
   if (!z || !dpred || !scale || !shift || !mean || !invstd || !w || !dwb || !workspace || !part) return MFPA_EINVAL;
-  if (npix < 0 || C < 4 || C > 256 || (C & (C - 1))) return MFPA_EINVAL;
-  hipStream_t s = mfpa_stream(stream);
-  const int nblk = grid_for(npix, (256 / (C / 4)) * 16, RED_BLOCKS);
-  hipLaunchKernelGGL(outconv_bwd_kernel<true>, dim3(nblk), dim3(256), 0, s, z, dpred, npix, C, scale, shift, w, (float*)nullptr, workspace,
-                     mean, invstd, part, z_is_bf16);
-  MFPA_CHECK_LAUNCH();
-  hipLaunchKernelGGL(colsum_finish_kernel, dim3((C + 1 + 3) / 4), dim3(256), 0, s, workspace, nblk, C + 1, dwb);
-  MFPA_CHECK_LAUNCH();
-  return MFPA_OK;
+  if (!outconv_shape_ok(npix, C)) return MFPA_EINVAL;
+  return outconv_bwd<true>(mfpa_stream(stream), z, dpred, npix, C, scale, shift, mean, invstd, w, nullptr, dwb, workspace, part, z_is_bf16);
 }
 
 int mfpa_l1_loss(const float* pred, const double* target, long long n, float* dpred, double* loss, double* workspace,

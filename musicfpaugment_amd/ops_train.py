@@ -267,9 +267,6 @@ DY16_MID = False            # True: a DoubleConv's inner gradient (dy of its fir
                             # at -0.07 ms of 31.2 (those two kernels are not bound by these bytes): off
 Z16_ACTIVATIONS = True      # plain-bf16 step (precision 2 with bf16 weight gradients): the convolutions' raw outputs z, the pooled activations and the
                             # transposed convolutions' outputs live in HBM as bfloat16 only (False: float32, A/B runs) -- see UNetTrainEngine._z16_for
-USE_BF16_DZ = True          # plain-bf16 step: input-gradient convolutions read the bf16 copy of dz (False: the float32 dz, A/B runs)
-FUSE_POOL_BWD_SUMS = True   # False: mfpa_maxpool2_bwd_add, then the BatchNorm backward's own reduction pass (chan_reduce_kernel<1>)
-RANK1_OUTCONV_BWD = True    # False: mfpa_outconv_bwd writes dy = dpred x w (1.06 GB per 64 clips), the BatchNorm backward reduces and reads it
 BF16_WGRAD_MIN_CH = 128     # plain-bf16 weight gradients: layers with at least this many channels on both sides read bf16 copies
 
 
@@ -729,7 +726,7 @@ class UNetTrainEngine:
         B, H, W, C = z.shape
         if dy.dtype == torch.bfloat16:
             dy = dy.float()                                            # (a bfloat16 skip gradient on the un-fused path: widened first)
-        if FUSE_POOL_BWD_SUMS and 256 % (C // 4) == 0:
+        if 256 % (C // 4) == 0:
             # the pass that finishes dy (skip gradient + routed pool gradient) also forms the partial sums of the BatchNorm
             # backward the block's _dconv_bwd starts with: no separate reduction pass over dy and z
             part = torch.empty((B * (H // 2), 2, C), dtype=torch.float32, device=z.device)
@@ -754,7 +751,7 @@ class UNetTrainEngine:
         wg16 = bf16_wgrad(cout, cout, self.wgrad_precision, r["xb3"] is not None)
         # plain bf16 step: when both consumers of dz (input-gradient convolution on conv_wd16_kernel, weight gradient) read its bf16
         # copy, the float32 dz is never written (mfpa_bn_relu_bwd(write_f32 = 0)) and the convolution's loader moves half the bytes
-        only16 = USE_BF16_DZ and self.precision == 2 and lay == 2 and wg16
+        only16 = self.precision == 2 and lay == 2 and wg16
         fused_pool = False
         if pool_dp is not None:
             z3, st3 = r["z3"], r["st3"]
@@ -787,7 +784,7 @@ class UNetTrainEngine:
         wg16_0 = cin0 > 0 and bf16_wgrad(cout, cin0, self.wgrad_precision, r["xb0"] is not None)
         c0_ = 0 if r["first_input"] is not None else r["src0"].shape[-1]
         c1_ = 0 if (r["first_input"] is not None or r["src1"] is None) else r["src1"].shape[-1]
-        only16_0 = (USE_BF16_DZ and self.precision == 2 and wg16_0 and need_input_grad and c0_ > 0
+        only16_0 = (self.precision == 2 and wg16_0 and need_input_grad and c0_ > 0
                     and weight_layout(H_, W_, cout, c0_, self.precision) == 2 and (c1_ == 0 or weight_layout(H_, W_, cout, c1_, self.precision) == 2))
         # activations as bfloat16 (Z16_ACTIVATIONS): dmid too leaves its convolution as bfloat16 only when the BatchNorm backward that reads
         # it writes nothing but the bf16 dz (and takes its two reductions from that convolution's epilogue)
@@ -850,7 +847,8 @@ class UNetTrainEngine:
         z, st = last["z3"], last["st3"]
         wb = self.P["outc.wb"]
         dy, dy_part, dy_rank1 = None, None, None
-        if RANK1_OUTCONV_BWD and st.drop[1] == 0:
+        if st.drop[1] == 0:
+            # dy = dpred x w is never written (the BatchNorm backward forms it again); the rank-1 form carries no dropout mask: else dy is materialised
             rows = ctypes.c_int(0)
             check(lib().mfpa_outconv_bwd_rows(_npix(z), 64, ctypes.byref(rows)), "mfpa_outconv_bwd_rows")
             dy_part = torch.empty((rows.value, 2, 64), dtype=torch.float32, device=z.device)

@@ -1242,6 +1242,33 @@ int mfpa_sosfilt(const void* x, int x_f64, int B, long long T, const double* sos
  * MFPA_EINVAL: a null pointer, or B, S or sos_per_row outside mfpa_sosfilt's rules. */
 int mfpa_sosfilt_work(int B, int S, int sos_per_row, long long* work_len);
 
+/* ---------------------------------------------------------------------------------------
+ * Room impulse responses (csrc/rir.hip): the image-source method for a shoebox room (Allen and Berkley), one room, source and
+ * microphone per row.  Additive to ABI 47.  Everything is float64.
+ *
+ * geom (B, 15) on the device: room Lx Ly Lz in metres, source, microphone, and the six energy absorption coefficients of the walls
+ * x0 x1 y0 y1 z0 z1.  The values are NOT checked (they live on the device; the Python layer checks them before the upload).
+ * Per axis and signed reflection index i in [-N, N], N = max_order:  p = i mod 2 (1 for odd i),  n = (i + p) / 2,  the image
+ * coordinate is s + i L for even i and -s + (i + 1) L for odd i,  X[i] = (image - mic)^2,  G[i] = beta0^|n - p| beta1^|n| with
+ * beta = sqrt(1 - alpha) of the axis's two walls.  Per image (ix, iy, iz) with |ix| + |iy| + |iz| <= N:
+ *   d = sqrt((X[ix] + Y[iy]) + Z[iz]),   amp = Gx Gy Gz / (4 pi d),   tau = (d fs) / c   (no fused multiply-add)
+ *   h[k] += amp w(k - tau) sinc(k - tau)  for 0 <= k < length,  w(x) = 0.5 (1 + cos(pi x / half)) for |x| <= half and 0 outside,
+ *   half = (filter_len - 1) / 2,  sinc(0) = 1
+ * Taps before sample 0 or from `length` on are dropped; an image at distance 0 or with gain 0 contributes nothing (no inf, no NaN
+ * from valid geometry).  out (B, ldo): row b holds h in its first `length` elements, float64 (out_f64 = 1) or float32, the float64
+ * value rounded once; reversed = 1 stores h[length - 1 - k] at k, which is what mfpa_fir takes as the taps of an impulse response.
+ * One workgroup owns 64 consecutive samples of one room; each of its four wavefronts adds the taps of every fourth image row ix in
+ * index order and the four partial sums are added in a fixed order: no atomics, the same bits from run to run, and a row's bits do
+ * not depend on B or on the row's position.
+ * MFPA_EINVAL before any launch, no pointer dereferenced on the host: B < 0 or B > 65535, max_order outside [0, 128], length outside
+ * [1, 262144], ldo < length, filter_len even or outside [3, 255], fs or c not finite or not positive, reversed / out_f64 other than
+ * 0 or 1, and with B > 0 a null or misaligned geom or out.  B == 0: MFPA_OK, no launch. */
+int mfpa_rir_shoebox(const double* geom, int B, int max_order, int length, double fs, double c, int filter_len, int reversed, int out_f64,
+                     void* out, long long ldo, void* stream);
+/* HOST function, no GPU work: *out = (2N + 1)(2N^2 + 2N + 3) / 3, the images with |ix| + |iy| + |iz| <= N = max_order.
+ * MFPA_EINVAL: a null pointer, max_order outside [0, 128]. */
+int mfpa_rir_image_count(int max_order, long long* out);
+
 #ifdef __cplusplus
 }
 #endif

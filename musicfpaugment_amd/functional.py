@@ -11,6 +11,10 @@ Two things differ from torchaudio, on purpose:
 The coefficient designs are the public Audio-EQ-Cookbook formulas (R. Bristow-Johnson) in the form torchaudio uses, as pure host
 functions in float64: `biquad_coefficients(kind, sample_rate, freq, Q, gain_db)`.  Orders above 2 go through ops.sosfilt as
 second-order sections; there is no tf2sos here.
+
+Beside the filters: `simulate_rir_ism` (torchaudio.prototype.functional's name; the shoebox image-source simulator of csrc/rir.hip,
+ops.simulate_rir) with the host helpers `eyring_absorption` and `rir_max_order`.  Parity with torchaudio and pyroomacoustics is
+unpinned there too; the pinned reference is tests/_rir_oracle.py.
 """
 from __future__ import annotations
 
@@ -166,3 +170,57 @@ def bass_biquad(waveform: torch.Tensor, sample_rate: int, gain: float, central_f
 def treble_biquad(waveform: torch.Tensor, sample_rate: int, gain: float, central_freq: float = 3000, Q: float = 0.707) -> torch.Tensor:
     """A high shelf: `gain` dB above central_freq."""
     return _design(waveform, "treble_biquad", "highshelf", sample_rate, central_freq, Q, gain)
+
+
+# ----------------------------------------------------------------------------- room impulse responses (csrc/rir.hip)
+def _rooms(room) -> np.ndarray:
+    room = np.asarray(room.detach().cpu().numpy() if isinstance(room, torch.Tensor) else room, dtype=np.float64)
+    if room.ndim not in (1, 2) or room.shape[-1] != 3:
+        raise ValueError(f"room must be (3,) or (B, 3), got {room.shape}")
+    if not (np.all(np.isfinite(room)) and np.all(room > 0.0)):
+        raise ValueError("every room side must be finite and positive")
+    return room
+
+
+def _rt60s(rt60, rooms: np.ndarray) -> np.ndarray:
+    rt60 = np.asarray(rt60, dtype=np.float64)
+    if not (np.all(np.isfinite(rt60)) and np.all(rt60 > 0.0)):
+        raise ValueError(f"rt60 must be finite and positive, got {rt60}")
+    try:
+        return np.broadcast_to(rt60, rooms.shape[:-1])
+    except ValueError:
+        raise ValueError(f"rt60 must be a scalar or one value per room, got {rt60.shape} for {rooms.shape[:-1]} rooms") from None
+
+
+def eyring_absorption(room, rt60):
+    """The uniform energy absorption coefficient that Eyring's formula gives a shoebox room (3,) or rooms (B, 3) for the decay time
+    rt60 in seconds: 1 - exp(-0.161 V / (S rt60)), V the volume, S the wall area.  A float, or (B,) float64; host arithmetic."""
+    room = _rooms(room)
+    rt60 = _rt60s(rt60, room)
+    V = room[..., 0] * room[..., 1] * room[..., 2]
+    S = 2.0 * (room[..., 0] * room[..., 1] + room[..., 1] * room[..., 2] + room[..., 0] * room[..., 2])
+    a = 1.0 - np.exp(-0.161 * V / (S * rt60))
+    return float(a) if a.ndim == 0 else a
+
+
+def rir_max_order(room, rt60, sound_speed: float = 343.0):
+    """The reflection order whose images reach past rt60 along the room's shortest side: ceil(c rt60 / min(L)).  An int, or (B,)
+    int64; host arithmetic."""
+    room = _rooms(room)
+    rt60 = _rt60s(rt60, room)
+    if not (math.isfinite(float(sound_speed)) and sound_speed > 0.0):
+        raise ValueError(f"sound_speed must be finite and positive, got {sound_speed}")
+    n = np.ceil(float(sound_speed) * rt60 / room.min(axis=-1)).astype(np.int64)
+    return int(n) if n.ndim == 0 else n
+
+
+def simulate_rir_ism(room, source, mic, max_order: int, absorption, output_length: int, *, sample_rate: float,
+                     sound_speed: float = 343.0, delay_filter_length: int = 81) -> torch.Tensor:
+    """torchaudio.prototype.functional.simulate_rir_ism for one microphone and frequency-independent walls: the image-source impulse
+    response of a shoebox room, (1, output_length) float32 on the GPU for room, source and mic of shape (3,), (B, output_length) for
+    (B, 3).  absorption is a scalar, (6,) or (B, 6), the walls in the order x0 x1 y0 y1 z0 z1 (west east south north floor ceiling).
+    Unlike torchaudio's, the length and the sample rate have no defaults, every image with |ix| + |iy| + |iz| <= max_order is summed
+    in float64, and the result is not normalised.  Parity with torchaudio and with pyroomacoustics is unpinned (neither is installed
+    where this is tested); the pinned reference is the numpy restatement in tests/_rir_oracle.py."""
+    return ops.simulate_rir(room, source, mic, absorption, max_order, output_length, sample_rate, sound_speed=sound_speed,
+                            filter_len=delay_filter_length)

@@ -1269,6 +1269,44 @@ int mfpa_rir_shoebox(const double* geom, int B, int max_order, int length, doubl
  * MFPA_EINVAL: a null pointer, max_order outside [0, 128]. */
 int mfpa_rir_image_count(int max_order, long long* out);
 
+/* ---------------------------------------------------------------------------------------
+ * Dynamic range compression (csrc/dynamics.hip): a feed-forward, log-domain compressor with the smooth decoupled peak detector of
+ * Giannoulis, Massberg and Reiss ("Digital Dynamic Range Compressor Design", JAES 2012), along the rows of (B, T) samples, one
+ * parameter set for the batch or one per row.  Additive to ABI 47.
+ *
+ * A parameter set is six float64 values: threshold_db (Th), slope s = 1 - 1/ratio in [0, 1] (a limiter has s = 1), knee_db W >= 0,
+ * attack_coef aA in [0, 1), release_coef aR in [0, 1), makeup_db M; a coefficient is exp(-1 / (seconds sample_rate)), formed by the
+ * caller, 0 for a time of 0.  A row has the state (y1, yL): (0, 0) or zi at the start, returned after sample T - 1 as zf.  Per
+ * sample, state and arithmetic float64, every product and sum rounded on its own (no fused multiply-add), in this order:
+ *   xg = 20 log10(max(|x|, 1e-10))
+ *   o  = xg - Th
+ *   xl = 0                        if 2 o <= -W
+ *        s (o + W/2)^2 / (2 W)    if 2 |o| < W
+ *        s o                      otherwise            (the gain reduction wanted, dB)
+ *   y1 = max(xl, aR y1 + (1 - aR) xl)                  (instant attack, smooth release)
+ *   yL = aA yL + (1 - aA) y1                           (attack smoothing)
+ *   y  = x 10^((M - yL) / 20)
+ * level_in = 0 is this formula; gr, when given, receives yL.  level_in = 1 takes x as xl itself, skips the first and the last
+ * line and stores yL in y (the envelope follower; no transcendental function); gr must be NULL.  The samples and both outputs are
+ * float32 (x_f64 = 0) or float64 (x_f64 = 1); a float32 output is the float64 value rounded once.
+ *   x, y, gr  (B, T) on the device, element aligned (4 or 8 bytes), not overlapping; gr may be NULL
+ *   params    (6,) with params_per_row = 0, (B, 6) with params_per_row = 1, float64 on the device.  The values are NOT checked (they
+ *             live on the device; the Python layer checks them before the upload)
+ *   apply     NULL, or B bytes on the device: row b with apply[b] == 0 is copied through bit for bit, its gr is 0 and its final
+ *             state is its initial state
+ *   zi, zf    NULL, or (B, 2) float64 on the device: (y1, yL)
+ * One workgroup of 8 wavefronts owns one row; a wavefront owns a contiguous part of it in whole super-chunks of 64 lanes x 16
+ * samples.  Both recurrences are scans over closed families of maps (y -> max(c, a y + b), and affine): a lane composes the maps of
+ * its 16 samples, a shuffle scan composes the lanes' maps, the map of everything before a lane is applied once to the carry, and
+ * the lane reruns its samples with the recurrence itself.  The row is walked three times with the parts' carries passed through
+ * LDS in wavefront order (csrc/dynamics.hip).  No atomics, no work buffer, no workgroup waits for another; a row's bits do not
+ * depend on B, on the row's position or on the run.
+ * MFPA_EINVAL before any launch, no pointer dereferenced on the host: B < 0 or B > 65535, T < 1 or T > 2^30, x_f64 /
+ * params_per_row / level_in other than 0 or 1, gr given with level_in = 1, and with B > 0 a null x, y or params or a misaligned
+ * pointer.  B == 0: MFPA_OK, no launch. */
+int mfpa_dynamics(const void* x, int x_f64, int B, long long T, const double* params, int params_per_row, const unsigned char* apply,
+                  const double* zi, double* zf, int level_in, void* y, void* gr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

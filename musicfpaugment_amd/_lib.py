@@ -225,6 +225,8 @@ _SIGNATURES = {
     "mfpa_sosfilt_work": ([c_int, c_int, c_int, c_void_p], c_int),
     "mfpa_rir_shoebox": ([c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p], c_int),
     "mfpa_rir_image_count": ([c_int, c_void_p], c_int),
+    "mfpa_dynamics": ([c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                       c_void_p], c_int),
 }
 
 

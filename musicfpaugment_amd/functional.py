@@ -15,6 +15,9 @@ second-order sections; there is no tf2sos here.
 Beside the filters: `simulate_rir_ism` (torchaudio.prototype.functional's name; the shoebox image-source simulator of csrc/rir.hip,
 ops.simulate_rir) with the host helpers `eyring_absorption` and `rir_max_order`.  Parity with torchaudio and pyroomacoustics is
 unpinned there too; the pinned reference is tests/_rir_oracle.py.
+
+And `compressor` / `limiter` with the host helper `compressor_params`: the dynamic range compressor of csrc/dynamics.hip
+(ops.compressor); the pinned reference is the definition restated in tests/_dynamics_oracle.py.
 """
 from __future__ import annotations
 
@@ -224,3 +227,57 @@ def simulate_rir_ism(room, source, mic, max_order: int, absorption, output_lengt
     where this is tested); the pinned reference is the numpy restatement in tests/_rir_oracle.py."""
     return ops.simulate_rir(room, source, mic, absorption, max_order, output_length, sample_rate, sound_speed=sound_speed,
                             filter_len=delay_filter_length)
+
+
+# ----------------------------------------------------------------------------- dynamic range compression (csrc/dynamics.hip)
+def compressor_params(sample_rate, threshold_db=-20.0, ratio=4.0, attack_ms=5.0, release_ms=100.0, knee_db=6.0,
+                      makeup_db=0.0) -> np.ndarray:
+    """What ops.compressor takes, from a compressor's front panel: (6,) float64 for numbers, (N, 6) when any value is a sequence of
+    N (the others are repeated).  slope = 1 - 1 / ratio (ratio >= 1, float("inf") is a limiter), the coefficients are
+    ops.time_coef(ms / 1000, sample_rate).  Host arithmetic.  ValueError: a ratio below 1 or NaN, a negative knee or time, a value
+    that is not finite, lengths that do not agree."""
+    vals = [np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+            for v in (threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db)]
+    if any(v.ndim > 1 for v in vals):
+        raise ValueError("every compressor parameter must be a number or have one entry per row")
+    try:
+        th, ratio, knee, attack, release, makeup = np.broadcast_arrays(*vals)
+    except ValueError:
+        raise ValueError(f"per-row compressor parameters must agree in length, got {[v.shape for v in vals]}") from None
+    if np.any(np.isnan(ratio)) or np.any(ratio < 1.0):
+        raise ValueError(f"ratio must be at least 1 (float('inf') for a limiter), got {ratio}")
+    q = np.empty(th.shape + (6,))
+    q[..., 0], q[..., 1], q[..., 2], q[..., 5] = th, 1.0 - 1.0 / ratio, knee, makeup
+    q[..., 3], q[..., 4] = ops.time_coef(attack / 1000.0, sample_rate), ops.time_coef(release / 1000.0, sample_rate)
+    return ops.dynamics_params(q)
+
+
+def _compress(waveform: torch.Tensor, q: np.ndarray, who: str) -> torch.Tensor:
+    if not isinstance(waveform, torch.Tensor) or waveform.dim() < 1 or waveform.dtype not in (torch.float32, torch.float64):
+        raise ValueError("waveform must be a float32 or float64 tensor (..., T)")
+    lead, T = waveform.shape[:-1], waveform.shape[-1]
+    n = int(np.prod(lead, dtype=np.int64))
+    if q.ndim == 2 and q.shape[0] != n:
+        raise ValueError(f"per-row parameters must have one entry per row ({n}), got {q.shape[0]}")
+    x = waveform
+    if not x.is_cuda:
+        if not torch.cuda.is_available():
+            raise MfpaError(f"{who} computes on the MI355X and none is present; no CPU fallback")
+        x = x.cuda()
+    with torch.cuda.device(x.device):
+        y = ops.compressor(x.reshape(-1, T), q)
+    return y.reshape(*lead, T).to(waveform.device)
+
+
+def compressor(waveform: torch.Tensor, sample_rate: int, threshold_db=-20.0, ratio=4.0, attack_ms=5.0, release_ms=100.0, knee_db=6.0,
+               makeup_db=0.0) -> torch.Tensor:
+    """A feed-forward dynamic range compressor (log-domain, smooth decoupled peak detector: Giannoulis, Massberg and Reiss, JAES
+    2012) along the last dimension of a (..., T) float32 or float64 waveform, in and out on the input's device, computed on the GPU
+    in float64 and rounded once.  Every parameter is a number or has one entry per row of the flattened leading dimensions."""
+    return _compress(waveform, compressor_params(sample_rate, threshold_db, ratio, attack_ms, release_ms, knee_db, makeup_db), "compressor")
+
+
+def limiter(waveform: torch.Tensor, sample_rate: int, threshold_db=-1.0, release_ms=50.0) -> torch.Tensor:
+    """A peak limiter: the compressor with slope 1 (ratio infinity), no knee and no attack time, so no output sample exceeds
+    10^(threshold_db / 20)."""
+    return _compress(waveform, compressor_params(sample_rate, threshold_db, float("inf"), 0.0, release_ms, 0.0, 0.0), "limiter")

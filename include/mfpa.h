@@ -1307,6 +1307,70 @@ int mfpa_rir_image_count(int max_order, long long* out);
 int mfpa_dynamics(const void* x, int x_f64, int B, long long T, const double* params, int params_per_row, const unsigned char* apply,
                   const double* zi, double* zf, int level_in, void* y, void* gr, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Delay lines (csrc/delay.hip): a time-varying fractional delay without feedback (echo, vibrato, chorus, a feed-forward flanger,
+ * wow and flutter, Doppler ramps) and a comb with an integer delay and feedback (the regenerating echo, the feed-forward comb, the
+ * Schroeder all-pass), along the rows of (B, T) samples.  Additive to ABI 47.
+ *
+ * mfpa_varidelay.  A row x[0..T) has V voices (1 <= V <= MFPA_DELAY_MAX_VOICES), voice v a gain g[v] and delays d[v][n] in samples
+ * (float64, negative = reading ahead), a dry gain g0, and an odd filter_len = 2 half + 1 in [3, 255].  Per output sample n, float64,
+ * every product and sum rounded on its own (no fused multiply-add), in this order:
+ *   acc = g0 * x[n]
+ *   for v in 0 .. V-1 (ascending):
+ *     p = (double)n - d[v][n]                                  (one rounding)
+ *     s = 0
+ *     if p > -(half + 1) and p < T + half:                     (false for a NaN; decided on the double, before any integer is formed)
+ *       whole = floor(p);  frac = p - whole                    (frac in [0, 1]; 1 only by rounding, for a tiny negative p)
+ *       sf = sinpi(frac);  cw = cospi(frac / half);  sw = sinpi(frac / half)
+ *       for j = -half .. half + 1 (ascending):                 (tap x[whole + j], 0 outside [0, T))
+ *         t = (double)j - frac
+ *         if |t| <= half:
+ *           w    = 0.5 * (1 + (cospi(j / half) * cw + sinpi(j / half) * sw))      (the Hann window 0.5 (1 + cos(pi t / half)))
+ *           sinc = 1 if t == 0 else (sf if j is odd else -sf) / (pi * t)          (sin(pi t) / (pi t))
+ *           s   += x[whole + j] * (w * sinc)
+ *     acc += g[v] * s
+ *   y[n] = acc, rounded once when y is float32
+ * A delay that is not finite, or a position whose window lies wholly outside the row, fails the comparison: that voice adds g[v] * 0
+ * at that sample.  Nothing is re-normalised: the windowed sinc's DC ripple (the taps of a fractional position do not sum to exactly 1) is the
+ * algorithm's own.  The interpolator does not band-limit: where the read position advances faster than one sample per sample, content above
+ * the new Nyquist frequency aliases (negligible for wow and flutter; a large constant ratio is mfpa_resample's job).
+ *   x        (B, ldx) on the device, float32 (x_f64 = 0) or float64, ldx >= T; not overlapping y
+ *   delay    float64 on the device; d[b][v][n] sits at delay[b * delay_row_stride + v * delay_voice_stride + n * delay_time_stride],
+ *            strides in elements, the row and voice strides >= 0, delay_time_stride 1, or 0: one constant delay per voice
+ *   gains    (B, V) float64 on the device;  dry (B,) float64 on the device.  The values are NOT checked (the Python layer does)
+ *   apply    NULL, or B bytes on the device: row b with apply[b] == 0 is copied through (bit for bit when y has x's type)
+ *   y        (B, T) on the device, float32 (y_f64 = 0) or float64
+ * A workgroup of four wavefronts produces MFPA_VARIDELAY_TILE consecutive outputs of one row, one per lane.  Per voice the tile
+ * reduces the smallest and largest live read position; if the window [floor(min p) - half, floor(max p) + half + 1] holds at most
+ * MFPA_VARIDELAY_WINDOW samples it is staged once in LDS as float64, zeros outside the row, and every tap reads LDS; otherwise the
+ * taps read global memory.  Both paths run the same arithmetic in the same order and give the same bits.  No atomics, no work
+ * buffer; a row's bits do not depend on B, on the row's position or on the path another tile took.
+ * MFPA_EINVAL before any launch, no pointer dereferenced on the host: B < 1 or B > 65535, T < 1 or T > 2^30, ldx < T, V outside
+ * [1, MFPA_DELAY_MAX_VOICES], filter_len even or outside [3, 255], a negative row or voice stride, delay_time_stride other than 0
+ * or 1, x_f64 / y_f64 other than 0 or 1, a null x, delay, gains, dry or y, a misaligned pointer. */
+#define MFPA_DELAY_MAX_VOICES 8
+#define MFPA_VARIDELAY_TILE 256
+#define MFPA_VARIDELAY_WINDOW 1024
+int mfpa_varidelay(const void* x, int x_f64, long long ldx, int B, long long T, const double* delay, long long delay_row_stride,
+                   long long delay_voice_stride, int delay_time_stride, int V, const double* gains, const double* dry,
+                   const unsigned char* apply, int filter_len, void* y, int y_f64, void* stream);
+/* mfpa_comb.  y[n] = b0 x[n] + (bD x[n - D] + aD y[n - D]), terms before the row's start 0; three products and two sums, each
+ * rounded on its own, the parentheses as written; float64 state (y[n - D] is the unrounded float64 value also when y is float32).
+ * b0 = 1, bD = 0: a regenerating echo;  aD = 0: a feed-forward comb;  b0 = -g, bD = 1, aD = g: Schroeder's all-pass.  There is no
+ * state across calls.
+ *   x        (B, ldx) on the device, float32 (x_f64 = 0) or float64;  y (B, T), float32 (y_f64 = 0) or float64, not overlapping x
+ *   params   (4,) with params_per_row = 0, (B, 4) with 1, float64 on the device: D, b0, bD, aD.  The values are NOT checked (the
+ *            Python layer does: D an integer in [1, 2^24], |aD| < 1); on the device D is truncated and clamped to [1, max_delay]
+ *   max_delay  the largest D of the call, [1, 2^24]: it sizes the grid
+ *   apply    as above
+ * The residue classes n mod D are independent first-order recurrences: the grid is (ceil(min(max_delay, T) / 256), B), lane r < D
+ * walks n = r, r + D, r + 2D, ... with its previous input and output in registers, loads and stores coalesced over consecutive
+ * residues; no synchronisation of any kind, and the same bits as the formula evaluated sample by sample.  A small D uses few lanes.
+ * MFPA_EINVAL before any launch: B < 1 or B > 65535, T < 1 or T > 2^30, ldx < T, max_delay outside [1, 2^24], x_f64 / y_f64 /
+ * params_per_row other than 0 or 1, a null x, params or y, a misaligned pointer. */
+int mfpa_comb(const void* x, int x_f64, long long ldx, int B, long long T, const double* params, int params_per_row, long long max_delay,
+              const unsigned char* apply, void* y, int y_f64, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -227,6 +227,9 @@ _SIGNATURES = {
     "mfpa_rir_image_count": ([c_int, c_void_p], c_int),
     "mfpa_dynamics": ([c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                        c_void_p], c_int),
+    "mfpa_varidelay": ([c_void_p, c_int, c_longlong, c_int, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_int, c_void_p, c_void_p,
+                        c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
+    "mfpa_comb": ([c_void_p, c_int, c_longlong, c_int, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_void_p], c_int),
 }
 
 

@@ -18,6 +18,9 @@ unpinned there too; the pinned reference is tests/_rir_oracle.py.
 
 And `compressor` / `limiter` with the host helper `compressor_params`: the dynamic range compressor of csrc/dynamics.hip
 (ops.compressor); the pinned reference is the definition restated in tests/_dynamics_oracle.py.
+
+And the delay-line effects of csrc/delay.hip: `echo`, `vibrato`, `chorus`, `flanger` and `wow_flutter` over ops.variable_delay,
+`comb`, `feedback_echo` and `allpass_comb` over ops.comb; the pinned reference is tests/_delay_oracle.py.
 """
 from __future__ import annotations
 
@@ -281,3 +284,153 @@ def limiter(waveform: torch.Tensor, sample_rate: int, threshold_db=-1.0, release
     """A peak limiter: the compressor with slope 1 (ratio infinity), no knee and no attack time, so no output sample exceeds
     10^(threshold_db / 20)."""
     return _compress(waveform, compressor_params(sample_rate, threshold_db, float("inf"), 0.0, release_ms, 0.0, 0.0), "limiter")
+
+
+# ----------------------------------------------------------------------------- delay-line effects (csrc/delay.hip)
+def _rate(sample_rate) -> float:
+    rate = float(sample_rate)
+    if not (math.isfinite(rate) and rate > 0.0):
+        raise ValueError(f"sample_rate must be positive, got {sample_rate}")
+    return rate
+
+
+def _numbers(who: str, **values) -> None:
+    """Each value one finite real number, a Python or numpy scalar."""
+    for name, v in values.items():
+        if not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+            raise ValueError(f"{who}: {name} must be one finite real number (a Python or numpy scalar), got {v!r}")
+
+
+def _on_rows(waveform: torch.Tensor, who: str, run) -> torch.Tensor:
+    """run(rows (N, T) on the GPU) for a (..., T) waveform on any device; the result goes back in the waveform's shape, on its device."""
+    if not isinstance(waveform, torch.Tensor) or waveform.dim() < 1 or waveform.dtype not in (torch.float32, torch.float64):
+        raise ValueError("waveform must be a float32 or float64 tensor (..., T)")
+    lead, T = waveform.shape[:-1], waveform.shape[-1]
+    x = waveform
+    if not x.is_cuda:
+        if not torch.cuda.is_available():
+            raise MfpaError(f"{who} computes on the MI355X and none is present; no CPU fallback")
+        x = x.cuda()
+    with torch.cuda.device(x.device):
+        y = run(x.reshape(-1, T))
+    return y.reshape(*lead, T).to(waveform.device)
+
+
+def comb_delay_samples(sample_rate, delay_ms) -> int:
+    """The comb's integer delay: delay_ms in samples rounded to the nearest, at least 1."""
+    rate = _rate(sample_rate)
+    _numbers("comb", delay_ms=delay_ms)
+    if delay_ms < 0.0:
+        raise ValueError(f"delay_ms must not be negative, got {delay_ms}")
+    return max(1, int(round(delay_ms * rate / 1000.0)))
+
+
+def echo(waveform: torch.Tensor, sample_rate, delays_ms, decays, gain_in: float = 1.0, gain_out: float = 1.0) -> torch.Tensor:
+    """sox `echo`, feed-forward: gain_out (gain_in x[n] + sum_k decays[k] x(n - delays_ms[k])) along the last dimension of a
+    (..., T) float32 or float64 waveform, up to ops.DELAY_MAX_VOICES echoes, the delays fractional (81-tap windowed sinc).  It is
+    ops.variable_delay(rows, [delays_ms[k] * sample_rate / 1000] as (N, V, 1) constant voices, gains=[gain_out * decays[k]],
+    dry=gain_out * gain_in): one launch, no (N, V, T) tensor."""
+    rate = _rate(sample_rate)
+    dl, dc = np.atleast_1d(np.asarray(delays_ms, dtype=np.float64)), np.atleast_1d(np.asarray(decays, dtype=np.float64))
+    if dl.ndim != 1 or dl.shape != dc.shape or not 1 <= dl.size <= ops.DELAY_MAX_VOICES:
+        raise ValueError(f"delays_ms and decays must have the same length, 1 to {ops.DELAY_MAX_VOICES}, got {dl.shape} and {dc.shape}")
+    _numbers("echo", gain_in=gain_in, gain_out=gain_out)
+    if not (np.all(np.isfinite(dl)) and np.all(np.isfinite(dc))) or np.any(dl < 0.0):
+        raise ValueError("delays_ms must be finite and not negative, decays finite")
+    return _on_rows(waveform, "echo", lambda rows: ops.variable_delay(
+        rows, np.broadcast_to((dl * rate / 1000.0)[:, None], (rows.shape[0], dl.size, 1)), gain_out * dc, dry=gain_out * gain_in))
+
+
+def comb(waveform: torch.Tensor, sample_rate, delay_ms, b0: float = 1.0, bD: float = 0.0, aD: float = 0.0) -> torch.Tensor:
+    """y[n] = b0 x[n] + (bD x[n - D] + aD y[n - D]), D = comb_delay_samples(sample_rate, delay_ms), |aD| < 1: it is
+    ops.comb(rows, D, b0, bD, aD)."""
+    D = comb_delay_samples(sample_rate, delay_ms)
+    q = ops.comb_params(D, b0, bD, aD)
+    if q.ndim != 1:
+        raise ValueError("b0, bD and aD must be numbers")
+    return _on_rows(waveform, "comb", lambda rows: ops.comb(rows, D, b0, bD, aD))
+
+
+def feedback_echo(waveform: torch.Tensor, sample_rate, delay_ms, feedback, mix: float = 1.0) -> torch.Tensor:
+    """A regenerating echo: wet[n] = x[n] + feedback wet[n - D], y = (1 - mix) x + mix wet, |feedback| < 1, D as in `comb`.  It is
+    ops.comb(rows, D, 1.0, -(1.0 - mix) * feedback, feedback); with mix = 1 the comb's pure feedback corner."""
+    _numbers("feedback_echo", feedback=feedback, mix=mix)
+    return comb(waveform, sample_rate, delay_ms, 1.0, -(1.0 - mix) * feedback, feedback)
+
+
+def allpass_comb(waveform: torch.Tensor, sample_rate, delay_ms, gain) -> torch.Tensor:
+    """Schroeder's all-pass: y[n] = -g x[n] + (x[n - D] + g y[n - D]), |g| < 1, unit magnitude at every frequency.  It is
+    ops.comb(rows, D, -gain, 1.0, gain)."""
+    _numbers("allpass_comb", gain=gain)
+    return comb(waveform, sample_rate, delay_ms, -gain, 1.0, gain)
+
+
+def vibrato(waveform: torch.Tensor, sample_rate, rate_hz: float = 5.0, depth_ms: float = 1.0) -> torch.Tensor:
+    """Pitch modulation: the row read at a delay of depth_ms (1 + sin(2 pi rate_hz t)), nothing dry.  It is
+    ops.variable_delay(rows, ops.lfo_delay(N, T, sample_rate, base_ms=depth_ms, depth_ms=depth_ms, rate_hz=rate_hz))."""
+    rate = _rate(sample_rate)
+    _numbers("vibrato", rate_hz=rate_hz, depth_ms=depth_ms)
+    if rate_hz < 0.0 or depth_ms < 0.0:
+        raise ValueError("rate_hz and depth_ms must not be negative")
+    return _on_rows(waveform, "vibrato", lambda rows: ops.variable_delay(
+        rows, ops.lfo_delay(rows.shape[0], rows.shape[1], rate, base_ms=depth_ms, depth_ms=depth_ms, rate_hz=rate_hz, device=rows.device)))
+
+
+def chorus_phases(voices: int) -> np.ndarray:
+    """The voices' oscillator phases, spread evenly over a period."""
+    return 2.0 * np.pi * np.arange(voices) / voices
+
+
+def chorus(waveform: torch.Tensor, sample_rate, voices: int = 3, base_ms: float = 20.0, depth_ms: float = 2.0, rate_hz: float = 0.8,
+           mix: float = 0.5) -> torch.Tensor:
+    """(1 - mix) x + mix / voices * sum_v x(n - d_v[n]), d_v = base_ms + depth_ms sin(2 pi rate_hz t + 2 pi v / voices).  It is
+    ops.variable_delay(rows, delay (N, voices, T), gains=mix / voices, dry=1 - mix) with delay[:, v] =
+    ops.lfo_delay(N, T, sample_rate, base_ms=base_ms, depth_ms=depth_ms, rate_hz=rate_hz, phase=chorus_phases(voices)[v])."""
+    rate = _rate(sample_rate)
+    if not isinstance(voices, int) or not 1 <= voices <= ops.DELAY_MAX_VOICES:
+        raise ValueError(f"voices must be an integer from 1 to {ops.DELAY_MAX_VOICES}, got {voices!r}")
+    _numbers("chorus", base_ms=base_ms, depth_ms=depth_ms, rate_hz=rate_hz, mix=mix)
+    if rate_hz < 0.0 or depth_ms < 0.0 or base_ms < depth_ms:
+        raise ValueError("rate_hz and depth_ms must not be negative and base_ms not below depth_ms")
+
+    def run(rows):
+        N, T = rows.shape
+        delay = torch.stack([ops.lfo_delay(N, T, rate, base_ms=base_ms, depth_ms=depth_ms, rate_hz=rate_hz, phase=float(ph), device=rows.device)
+                             for ph in chorus_phases(voices)], dim=1)
+        return ops.variable_delay(rows, delay, mix / voices, dry=1.0 - mix)
+    return _on_rows(waveform, "chorus", run)
+
+
+def flanger(waveform: torch.Tensor, sample_rate, base_ms: float = 1.0, depth_ms: float = 2.0, rate_hz: float = 0.5,
+            mix: float = 0.7) -> torch.Tensor:
+    """A feed-forward flanger: x[n] + mix x(n - d[n]), d sweeping from base_ms to base_ms + depth_ms at rate_hz.  It is
+    ops.variable_delay(rows, ops.lfo_delay(N, T, sample_rate, base_ms=base_ms + depth_ms / 2, depth_ms=depth_ms / 2,
+    rate_hz=rate_hz), gains=mix, dry=1.0).  torchaudio.functional.flanger's `regen` (feedback through the moving delay) is not
+    offered, its interpolation and wave shapes differ, and parity with torchaudio is unpinned."""
+    rate = _rate(sample_rate)
+    _numbers("flanger", base_ms=base_ms, depth_ms=depth_ms, rate_hz=rate_hz, mix=mix)
+    if rate_hz < 0.0 or depth_ms < 0.0 or base_ms < 0.0:
+        raise ValueError("base_ms, depth_ms and rate_hz must not be negative")
+    return _on_rows(waveform, "flanger", lambda rows: ops.variable_delay(
+        rows, ops.lfo_delay(rows.shape[0], rows.shape[1], rate, base_ms=base_ms + depth_ms / 2, depth_ms=depth_ms / 2, rate_hz=rate_hz,
+                            device=rows.device), mix, dry=1.0))
+
+
+def wow_flutter(waveform: torch.Tensor, sample_rate, wow_hz: float = 0.8, wow_depth: float = 0.002, flutter_hz: float = 8.0,
+                flutter_depth: float = 0.0008, phase=(0.0, 0.0)) -> torch.Tensor:
+    """The speed drift of an analogue playback chain: the row played at the relative speed
+    1 + wow_depth sin(2 pi wow_hz t + phase[0]) + flutter_depth sin(2 pi flutter_hz t + phase[1]).  It is
+    ops.variable_delay(rows, ops.speed_drift_delay(N, T, sample_rate, [(wow_depth, wow_hz, phase[0]), (flutter_depth, flutter_hz,
+    phase[1])])); with both depths 0 the delay is 0 and finite samples come back with their bits, up to the sign of a zero
+    (a sample that is not finite spreads over the filter's length as NaN, as in any FIR).  The interpolator does not band-limit,
+    which is negligible at these depths; for a large constant speed change use transforms.Speed."""
+    rate = _rate(sample_rate)
+    if len(phase) != 2:
+        raise ValueError("phase is (wow phase, flutter phase)")
+    _numbers("wow_flutter", wow_hz=wow_hz, wow_depth=wow_depth, flutter_hz=flutter_hz, flutter_depth=flutter_depth, wow_phase=phase[0],
+             flutter_phase=phase[1])
+    if wow_hz < 0.0 or flutter_hz < 0.0 or not (abs(wow_depth) + abs(flutter_depth) < 1.0):
+        raise ValueError("the frequencies must not be negative and the depths must sum to less than 1")
+    return _on_rows(waveform, "wow_flutter", lambda rows: ops.variable_delay(
+        rows, ops.speed_drift_delay(rows.shape[0], rows.shape[1], rate, [(wow_depth, wow_hz, phase[0]), (flutter_depth, flutter_hz, phase[1])],
+                                    device=rows.device)))

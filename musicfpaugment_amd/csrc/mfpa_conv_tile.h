@@ -88,6 +88,12 @@ constexpr int PT = 8;                                                  // 16-pix
 constexpr int OUTBUF = PH * PW * 64 * 4;                               // the epilogue's LDS tile: 256 px x 64 ch fp32, piece (pixel m, channel quad q) at m * 256 + ((q ^ (m & 15)) << 4)
 
 __device__ __forceinline__ constexpr int plane_off(int hl, int kg) { return hl * HLS + kg * PLANE + (kg >> 1) * 128; }
+
+// Both kernels' 16-pixel groups are pixels TWO columns apart, so the loaders stage a halo row's columns DE-INTERLEAVED -- the 17 even halo
+// columns, then the 17 odd ones -- and a group's fragment is still 16 consecutive 16-byte pieces of a plane: halo column hx sits at staged
+// position (hx & 1) * HALF + (hx >> 1) of its row, staged position `pos` holds halo column halo_col(pos).
+constexpr int HALF = HPW / 2;
+__device__ __forceinline__ constexpr int halo_col(int pos) { return pos < HALF ? 2 * pos : 2 * (pos - HALF) + 1; }
 }  // namespace role_split
 
 }  // namespace mfpa_tile

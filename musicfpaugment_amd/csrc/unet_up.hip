@@ -31,9 +31,8 @@ namespace mfpa_unet {
 namespace {
 
 using namespace mfpa_tile;
-using namespace mfpa_tile::role_split;     // tile geometry and LDS plane layout (shared with conv_ws64_kernel); PT's group index here: 4 * px + j (column parity, row pair)
+using namespace mfpa_tile::role_split;     // tile geometry, LDS plane layout and de-interleaved halo columns (shared with conv_ws64_kernel); PT's group index here: 4 * px + j (column parity, row pair)
 
-constexpr int HALF = HPW / 2;                                          // a staged halo row: 17 even halo columns, then the 17 odd ones
 constexpr int LPH = PH / 2 + 2, LPW = PW / 2 + 2, LP = LPH * LPW;      // the low-resolution patch: 6 x 18
 constexpr int L_F4 = (LP + PPI - 1) / PPI;                             // staging slots per loader thread and low-resolution chunk (4; skip chunk: A_F4)
 constexpr int EPI_FLOATS = 64 + 16 * 64;                               // [shift 64 | bias table 4 x 4 x 64]
@@ -96,7 +95,7 @@ __global__ __launch_bounds__(THREADS, 1) void conv_up_kernel(UpArgs a) {
 #pragma unroll
         for (int it = 0; it < A_F4; ++it) {
           const int pix = pl + it * PPI;
-          const int pos = pix % HPW, hx = pos < HALF ? 2 * pos : 2 * (pos - HALF) + 1;
+          const int hx = halo_col(pix % HPW);
           const int gy = T.y0 + pix / HPW - 1, gx = T.x0 + hx - 1;
           T.ain |= ((pix < HP && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? 1u : 0u) << it;
         }
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(THREADS, 1) void conv_up_kernel(UpArgs a) {
 #pragma unroll
     for (int it = 0; it < A_F4; ++it) {
       const int pix = pl + it * PPI;
-      const int pos = pix % HPW, hx = pos < HALF ? 2 * pos : 2 * (pos - HALF) + 1;
+      const int hx = halo_col(pix % HPW);
       off0[it] = pix < HP ? (unsigned)(((pix / HPW) * a.W + hx) * a.Cs + 4 * aq) * 4u : 0xfffffff0u;
     }
 #pragma unroll

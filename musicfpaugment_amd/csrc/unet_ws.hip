@@ -21,7 +21,9 @@
 // ~6 k cycles, a quarter of a two-chunk tile) and, for up4's second layer, the fused OutConv's 64-channel dot product per pixel.
 // One s_barrier per 32-channel chunk hands a finished stage to the compute waves and a read-out stage back to the loaders.  The tile loop
 // is persistent (one workgroup per CU walks tiles b, b + G, ...): the loaders simply run on into the next tile's first chunk.
-// LDS: two stages of eight planes [hi | lo][k-group] of (pixel x 16 B), the layout conv_wd16_kernel reads (conflict-free ds_read_b128).
+// LDS: two stages of eight planes [hi | lo][k-group] of (halo pixel x 16 B) (conflict-free ds_read_b128), a halo row's columns de-interleaved
+// (even, then odd: mfpa_conv_tile.h) because a compute wave's 16-pixel groups are pixels two columns apart -- the column-odd groups at one
+// tap and the column-even groups at the next tap of the row then want the same fragments, and a chunk costs 12 sets of reads, not 18.
 // Same products and the same summation inside an instruction as conv_wd16_kernel: bit-identical outputs (tests/test_gpu_unet.py).
 #include "mfpa_common.h"
 #include "mfpa_conv_tile.h"
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
 #pragma unroll
         for (int it = 0; it < A_F4; ++it) {
           const int pix = lt / SPP + it * PPI;
-          const int gy = T.y0 + pix / HPW - 1, gx = T.x0 + pix % HPW - 1;
+          const int gy = T.y0 + pix / HPW - 1, gx = T.x0 + halo_col(pix % HPW) - 1;   // (staged position -> halo column: see off0 / off1 below)
           const bool in = pix < HP && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
           const int y1 = gy - a.oy1, x1 = gx - a.ox1;
           const bool in1 = in && y1 >= 0 && y1 < a.H1 && x1 >= 0 && x1 < a.W1;
@@ -119,7 +121,9 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
     const bool has_duty = a.y != nullptr || a.w1x1 != nullptr;
     // the epilogue's memory work for tile `t` out of the LDS tile the compute waves filled (see the header): the 64-channel rows as
     // 1 KB-per-wave coalesced stores (16 lanes = the 16 channel quads of a pixel, 4 pixels per wave instruction), then -- fused OutConv
-    // -- one pixel per loader thread: 64 channels x their weights + bias
+    // -- one pixel per loader thread: 64 channels x their weights + bias.  The compute waves write the tile in THEIR group order: linear pixel
+    // n = 32 row + column of the tile sits at LDS position m = (row >> 2) * 128 + ((column & 1) * 4 + (row & 3)) * 16 + (column >> 1), written
+    // below as a per-thread part + a per-pass constant (as one expression of n hipcc kept an address pair per pass and spilled).
     auto duty = [&](int t) __attribute__((always_inline)) {
       int bx = __builtin_amdgcn_readfirstlane(t);
       const int tx = bx % a.tiles_x; bx /= a.tiles_x;
@@ -131,18 +135,21 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
         // the 16-byte lo piece: the next convolution's loaders only copy
         char* yb = reinterpret_cast<char*>(a.y + (size_t)bx * a.H * a.W * a.Cout + n0);
         const int kg8 = lt & 7;                                      // channels 8 kg8 .. 8 kg8 + 7 of this workgroup's 64
+        const int col = lt >> 3;                                     // a pass is one tile row: m = (row >> 2) * 128 + (row & 3) * 16 + mt, m & 15 = col >> 1
+        const char* const ob = outbuf + ((col & 1) * 64 + (col >> 1)) * 256;
+        const int pc0 = ((2 * kg8) ^ (col >> 1)) << 4, pc1 = ((2 * kg8 + 1) ^ (col >> 1)) << 4;
         for (int pass = 0; pass < 8; pass += 2) {
           f32x4 v[2][2];
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
-            const int m = (pass + u) * 32 + (lt >> 3);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) v[u][h] = *reinterpret_cast<const f32x4*>(outbuf + m * 256 + (((2 * kg8 + h) ^ (m & 15)) << 4));
+            const int mrow = ((pass + u) >> 2) * 128 + ((pass + u) & 3) * 16;
+            v[u][0] = *reinterpret_cast<const f32x4*>(ob + mrow * 256 + pc0);
+            v[u][1] = *reinterpret_cast<const f32x4*>(ob + mrow * 256 + pc1);
           }
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
-            const int m = (pass + u) * 32 + (lt >> 3);
-            const int gy = ey0 + m / PW, gx = ex0 + m % PW;
+            const int n = (pass + u) * 32 + (lt >> 3);
+            const int gy = ey0 + n / PW, gx = ex0 + n % PW;
             unsigned hi[4], lo[4];
 #pragma unroll
             for (int h = 0; h < 2; ++h)
@@ -158,18 +165,22 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
         }
       } else if (a.y != nullptr) {
         char* yb = reinterpret_cast<char*>(a.y + (size_t)bx * a.H * a.W * a.Cout + n0);
-        const int q = lt & 15;
+        const int q = lt & 15, c4 = lt >> 4;
+        // pass P = pass + u holds tile row P >> 1, columns (P & 1) * 16 + c4: m = (P >> 3) * 128 + ((P >> 1) & 3) * 16 + (P & 1) * 8 + mt with
+        // mt = (c4 & 1) * 64 + (c4 >> 1), m & 15 = (c4 >> 1) + 8 (P & 1) -- the piece's swizzle has two values per thread
+        const char* const ob0 = outbuf + ((c4 & 1) * 64 + (c4 >> 1)) * 256 + ((q ^ (c4 >> 1)) << 4);
+        const char* const ob1 = outbuf + ((c4 & 1) * 64 + (c4 >> 1) + 8) * 256 + ((q ^ (c4 >> 1) ^ 8) << 4);
         for (int pass = 0; pass < 16; pass += 4) {                  // four LDS reads in flight, then their four stores
           f32x4 v[4];
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
-            const int m = (pass + u) * 16 + (lt >> 4);
-            v[u] = *reinterpret_cast<const f32x4*>(outbuf + m * 256 + ((q ^ (m & 15)) << 4));
+            const int mrow = (pass >> 3) * 128 + (((pass >> 1) & 3) + (u >> 1)) * 16;
+            v[u] = *reinterpret_cast<const f32x4*>(((u & 1) ? ob1 : ob0) + mrow * 256);
           }
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
-            const int m = (pass + u) * 16 + (lt >> 4);
-            const int gy = ey0 + m / PW, gx = ex0 + m % PW;
+            const int n = (pass + u) * 16 + (lt >> 4);
+            const int gy = ey0 + n / PW, gx = ex0 + n % PW;
             if (gy < a.H && gx < a.W) *reinterpret_cast<f32x4*>(yb + (((unsigned)gy * (unsigned)a.W + (unsigned)gx) * (unsigned)a.Cout + 4u * (unsigned)q) * 4u) = v[u];
           }
         }
@@ -190,13 +201,16 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) sum = fmaf(v[u][k], w[u][k], sum);
         }
-        const int gy = ey0 + m / PW, gx = ex0 + m % PW;
+        // (the thread takes LDS POSITION m -- a wave instruction's 16-lane quarters keep 16 different m & 15: conflict-free -- which holds
+        //  pixel (row, column) = (4 (m >> 7) + ((m >> 4) & 3), 2 (m & 15) + ((m >> 6) & 1)) of the tile)
+        const int gy = ey0 + 4 * (m >> 7) + ((m >> 4) & 3), gx = ex0 + 2 * (m & 15) + ((m >> 6) & 1);
         if (gy < a.H && gx < a.W) a.y1x1[((size_t)bx * a.H + gy) * a.W + gx] = sum + a.b1x1;
       }
     };
 
     if constexpr (!C1SRC) {
-      // a thread's staging slots map to fixed halo pixels (pix = lt / 8 + 32 it); their byte offsets relative to the tile's HALO ORIGIN do
+      // a thread's staging slots map to fixed STAGED positions (pix = lt / 8 + 32 it: halo row pix / HPW, and in it halo column
+      // halo_col(pix % HPW) -- the even columns, then the odd ones: mfpa_conv_tile.h); their byte offsets relative to the tile's HALO ORIGIN do
       // not depend on the tile (registers: the loader waves have room).  Raw buffer loads through a per-clip descriptor.  Edge tiles: halo
       // rows above / below the image fall outside the clip and return zero by themselves, a slot left / right of the image (or in a padded
       // column of the smaller source 1) is requested at an offset beyond the clip instead -- nothing is masked when it is split.
@@ -204,7 +218,7 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
 #pragma unroll
       for (int it = 0; it < A_F4; ++it) {
         const int pix = lt / SPP + it * PPI;
-        const int py = pix / HPW, px = pix % HPW;
+        const int py = pix / HPW, px = halo_col(pix % HPW);
         off0[it] = (unsigned)((py * a.W + px) * a.C0 + 4 * aq) * 4u;
         off1[it] = (unsigned)((py * a.W1 + px) * a.C1 + 4 * aq) * 4u;
         // a PADDING slot (pix >= HP: halo row PH + 2, which an interior tile's clip need not contain) is never inside: its VECTOR offset lies
@@ -356,12 +370,13 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
         Alo[t] = __builtin_bit_cast(s16x4, uint2{l0, l1});
       }
       // per lane, tile-independent: where pixel p of pixel tile t sits in the wave's patch (tap (0, 0)), its halo coordinates, and the
-      // patch displacement of the lane's four taps
+      // patch displacement of the lane's four taps.  A pixel tile is 16 consecutive STAGED positions hp (the generic loader's order: halo
+      // row hp / HPW, halo column halo_col(hp % HPW)), so produce() stores pixel p of tile t at position (pt0 + t) * 16 + p as it stands.
       int pbase[6], pyx[6];
 #pragma unroll
       for (int t = 0; t < 6; ++t) {
         const int hp = (pt0 + (t < npt ? t : 0)) * 16 + p;
-        const int py = hp / HPW, px = hp % HPW;
+        const int py = hp / HPW, px = halo_col(hp % HPW);
         pbase[t] = (py - hr0) * C1W + px;
         pyx[t] = (py << 8) | px | (hp < HP ? 0 : 0x10000);
       }
@@ -485,24 +500,37 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
   const int p = lane & 15, g = lane >> 4;
 
   bf16x8 wq[3][2][2];                                                  // weight fragments: ring of three sets, [slot][16-channel tile][hi, lo]
+  // through raw buffer loads, as in conv_up_kernel: the image's descriptor in scalar registers, ONE vector offset (lane * 16) for every load,
+  // the (tap, chunk, channel-tile) block offset in the instruction's scalar offset -- no 64-bit vector address per request
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (int)(9u * (unsigned)a.Cout * (unsigned)Cin * 4u), 0x00020000);
+  const unsigned wrow = (unsigned)(a.Cout / 16), wcol = (unsigned)(n0 / 16 + 2 * wn);
+  const int wlane = lane * 16;
   auto load_w = [&](int chunk, int tap, auto SLOT) __attribute__((always_inline)) {
     constexpr int slot = decltype(SLOT)::value;
-    const char* wb = reinterpret_cast<const char*>(a.w) + ((((size_t)tap * nchunks + chunk) * (size_t)(a.Cout / 16) + (size_t)(n0 / 16 + 2 * wn)) << 11) + lane * 16;
-    wq[slot][0][0] = *reinterpret_cast<const bf16x8*>(wb);
-    wq[slot][0][1] = *reinterpret_cast<const bf16x8*>(wb + 1024);
-    wq[slot][1][0] = *reinterpret_cast<const bf16x8*>(wb + 2048);
-    wq[slot][1][1] = *reinterpret_cast<const bf16x8*>(wb + 3072);
+    const int so = (int)__builtin_amdgcn_readfirstlane((int)((((unsigned)tap * (unsigned)nchunks + (unsigned)chunk) * wrow + wcol) << 11));
+    wq[slot][0][0] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, wlane, so, 0));
+    wq[slot][0][1] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, wlane + 1024, so, 0));
+    wq[slot][1][0] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, wlane + 2048, so, 0));
+    wq[slot][1][1] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, wlane + 3072, so, 0));
   };
   struct XFrags { bf16x8 h[4], l[4]; };
-  XFrags fx0, fx1;
-  const int xbase = ((4 * wm) * HPW + p) * 16 + plane_off(0, g);      // the lane's row of pixel tile 0 in plane (hi, g) at tap (0, 0)
-  auto tile_disp = [](int pt) { return ((pt >> 1) * HPW + (pt & 1) * 16) * 16; };
-  auto read_x = [&](XFrags& f, const char* stage, int tap_off, int half) __attribute__((always_inline)) {
+  XFrags fx[2];
+  // Pixel group pt = 4 px + j of the wave: tile row 4 wm + j, columns 2 p + px (conv_up_kernel's order: 16 pixels two columns apart).  Its
+  // fragment at tap (ta, tb) is halo row 4 wm + j + ta, halo column 2 p + s with s = px + tb -> staged position (s & 1) * HALF + (s >> 1) + p
+  // of that row: only s enters the address, so the column-odd groups at tap (ta, tb) and the column-even groups at tap (ta, tb + 1) read the
+  // same bytes, and a tap row's six half-steps read FOUR distinct fragment sets s = 0 .. 3 (feeding 1, 2, 2, 1 consecutive half-steps) --
+  // 12 sets of eight reads per chunk, not 18.  Set d = 4 ta + s of a chunk lives in fx[d & 1] (twelve sets: every chunk starts in fx[0]).
+  // The next set's eight reads go under the half-steps that use the current one: all under a sole user, groups 0, 1 / 2, 3 under a first /
+  // second user.  Which pixels share an instruction does not enter a pixel's sum: the outputs are bit for bit those of one read per half-step.
+  const int xbase = ((4 * wm) * HPW + p) * 16 + plane_off(0, g);      // the lane's piece of row-0 group at set (0, 0) in plane (hi, g)
+  constexpr int R_ALL = 0, R_FIRST = 1, R_SECOND = 2;                  // which groups of a set one half-step reads: 0 .. 3, 0 .. 1, 2 .. 3
+  auto read_set = [&](XFrags& f, const char* stage, auto TA, auto S, auto PART) __attribute__((always_inline)) {
+    constexpr int ta = decltype(TA)::value, s = decltype(S)::value, part = decltype(PART)::value;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const char* r = stage + xbase + tile_disp(4 * half + i) + tap_off;
-      f.l[i] = *reinterpret_cast<const bf16x8*>(r + HLS);
-      f.h[i] = *reinterpret_cast<const bf16x8*>(r);
+    for (int j = (part == R_SECOND ? 2 : 0); j < (part == R_FIRST ? 2 : 4); ++j) {
+      const char* r = stage + xbase + ((ta + j) * HPW + (s & 1) * HALF + (s >> 1)) * 16;
+      f.l[j] = *reinterpret_cast<const bf16x8*>(r + HLS);
+      f.h[j] = *reinterpret_cast<const bf16x8*>(r);
     }
   };
   floatx4 acc[2][PT];                                                  // per tile they start as the C operand of their first MFMA (see `initv`); the one
@@ -514,7 +542,8 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
   // that the epilogue is a bare ReLU.  They enter as the C operand of an accumulator's FIRST MFMA of a tile (tap 0 of chunk 0 is its own
   // code: FIRST), so no accumulator is ever initialised by vector moves.  (Filled behind the first barrier: `epi` is written above.)
   floatx4 initv[2];
-  auto mfma_half = [&](const XFrags& f, const bf16x8 (&w)[2][2], int half, auto FIRST) __attribute__((always_inline)) {
+  auto mfma_half = [&](const XFrags& f, const bf16x8 (&w)[2][2], auto HALFI, auto FIRST) __attribute__((always_inline)) {
+    constexpr int half = decltype(HALFI)::value;                       // column parity px of the four groups
     // term-major (lo x hi, hi x lo, hi x hi -- conv_wd16_kernel's order: bit-identical sums): an accumulator is touched every eighth instruction
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
@@ -530,43 +559,56 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[ct][4 * half + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[ct][0], f.h[i], acc[ct][4 * half + i], 0, 0, 0);
   };
-  constexpr int N_R = 8, N_M = 24, N_W = 4;                            // fragment reads / MFMAs of one phase, weight loads of one tap
-  // One tap.  Phase A: MFMA(pixel tiles 0..3 of tap t) || read tiles 4..7 of tap t, request the weights of tap t + 2.  Phase B: MFMA(tiles
-  // 4..7) || read tiles 0..3 of tap t + 1.  The chunk's one barrier sits between the phases of tap 8: behind it the other stage is complete
-  // (the loaders arrived) and this one is read out (every compute wave's fragment reads of it have returned: lgkmcnt(0) in front of it).
+  constexpr int N_M = 24, N_W = 4;                                     // MFMAs of one half-step, weight loads of one tap
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using RAll = std::integral_constant<int, R_ALL>;
+  using RFirst = std::integral_constant<int, R_FIRST>;
+  using RSecond = std::integral_constant<int, R_SECOND>;
+  // One tap (ta, tb), b = tb & 1.  Half A (column-even groups, set s = tb in fx[b]): MFMA || read set s + 1 into fx[b ^ 1] -- all of it when
+  // tb = 0 (set 0 has this one user), else groups 2, 3 (half B of the previous tap read groups 0, 1) -- and request the weights of tap t + 2.
+  // Half B (column-odd groups, set s = tb + 1 in fx[b ^ 1]): MFMA || read groups 0, 1 of set s + 1 into fx[b], or, when tb = 2 (set 3 has this
+  // one user), all of the next tap row's set 0.  The chunk's one barrier sits between the halves of tap 8: behind it the other stage is
+  // complete (the loaders arrived) and this one is read out (every compute wave's fragment reads of it have returned: lgkmcnt(0) in front of
+  // it); half B of tap 8 reads the next chunk's set 0 out of that other stage.
   int kpar = 0;                                                        // parity of the stage the current chunk is read from
   auto tap_body = [&](auto TAP, int chunk, auto FIRST) __attribute__((always_inline)) {
-    constexpr int tap = decltype(TAP)::value;
-    constexpr int ntap = (tap + 1) % TAPS;
-    constexpr int tap_off = ((tap / 3) * HPW + (tap % 3)) * 16, ntap_off = ((ntap / 3) * HPW + (ntap % 3)) * 16;
+    constexpr int tap = decltype(TAP)::value, ta = tap / 3, tb = tap % 3, b = tb & 1;
+    using TA = std::integral_constant<int, ta>;
+    using PART_A = std::conditional_t<tb == 0, RAll, RSecond>;
+    using PART_B = std::conditional_t<tb == 2, RAll, RFirst>;
+    constexpr int n_ra = tb == 0 ? 8 : 4, n_rb = tb == 2 ? 8 : 4;      // fragment reads (16 bytes each) under half A / half B
     const int chunk_n = chunk + 1 < nchunks ? chunk + 1 : 0;
     const char* cur = smem + kpar * STAGE;
-    const char* nxt = (tap == TAPS - 1) ? smem + (kpar ^ 1) * STAGE : cur;
-    read_x(fx1, cur, tap_off, 1);
-    mfma_half(fx0, wq[tap % 3], 0, FIRST);
+    read_set(fx[b ^ 1], cur, TA{}, std::integral_constant<int, tb + 1>{}, PART_A{});
+    mfma_half(fx[b], wq[tap % 3], I0{}, FIRST);
     load_w((tap + 2 >= TAPS) ? chunk_n : chunk, (tap + 2) % TAPS, std::integral_constant<int, (tap + 2) % 3>{});
-    pin_reads<N_M - 1, N_R>();
-    constexpr int used_a = pin_read_slots(N_M - 1, N_R);
+    pin_reads<N_M - 1, n_ra>();
+    constexpr int used_a = pin_read_slots(N_M - 1, n_ra);
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
     __builtin_amdgcn_sched_group_barrier(0x020, N_W, 0);
     if constexpr (N_M - used_a - 1 > 0) __builtin_amdgcn_sched_group_barrier(0x008, N_M - used_a - 1, 0);
     __builtin_amdgcn_sched_barrier(0);
-    if (tap == TAPS - 1) {
+    if constexpr (tap == TAPS - 1) {
       __syncthreads();                                                 // (tried instead in round 5, code retired: hand-offs through LDS progress counters
                                                                        //  with no barrier in the loop -- did not move the kernel; DESIGN.md section 7, NOTES round 5)
       __builtin_amdgcn_sched_barrier(0);
+      read_set(fx[b], smem + (kpar ^ 1) * STAGE, I0{}, I0{}, RAll{});
+    } else if constexpr (tb == 2) {
+      read_set(fx[b], cur, std::integral_constant<int, ta + 1>{}, I0{}, RAll{});
+    } else {
+      read_set(fx[b], cur, TA{}, std::integral_constant<int, tb + 2>{}, RFirst{});
     }
-    read_x(fx0, nxt, ntap_off, 0);
-    mfma_half(fx1, wq[tap % 3], 1, FIRST);
-    pin_reads<N_M, N_R>();
-    if constexpr (N_M - pin_read_slots(N_M, N_R) > 0) __builtin_amdgcn_sched_group_barrier(0x008, N_M - pin_read_slots(N_M, N_R), 0);
+    mfma_half(fx[b ^ 1], wq[tap % 3], I1{}, FIRST);
+    pin_reads<N_M, n_rb>();
+    if constexpr (N_M - pin_read_slots(N_M, n_rb) > 0) __builtin_amdgcn_sched_group_barrier(0x008, N_M - pin_read_slots(N_M, n_rb), 0);
     __builtin_amdgcn_sched_barrier(0);
   };
 
   load_w(0, 0, std::integral_constant<int, 0>{});
   load_w(0, 1, std::integral_constant<int, 1>{});
   __syncthreads();                                                     // stage 0 holds chunk 0 of the first tile
-  read_x(fx0, smem, 0, 0);
+  read_set(fx[0], smem, I0{}, I0{}, RAll{});
   for (int ti = 0; ti < owned; ++ti) {
     int bx = __builtin_amdgcn_readfirstlane(tile_of((int)blockIdx.x, ti, G));
     const int tx = bx % a.tiles_x; bx /= a.tiles_x;
@@ -610,8 +652,9 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
           for (int j = 0; j < 4; ++j) acc[ct][pt][j] = fmaxf(acc[ct][pt][j], 0.f);
     }
     if (a.y != nullptr || a.w1x1 != nullptr) {
-      // the tile goes to LDS as 16-byte pieces (pixel m, channel quad q) at m * 256 + ((q ^ (m & 15)) << 4): a wave instruction's 16 pixels
-      // of one quad hit 16 different 16-byte bank groups; the loaders store it (and form the fused OutConv) one barrier from now
+      // the tile goes to LDS as 16-byte pieces (position m = the wave's group order, channel quad q) at m * 256 + ((q ^ (m & 15)) << 4): a wave
+      // instruction's 16 pixels of one quad hit 16 different 16-byte bank groups; the loaders un-permute (their `duty`), store it and form
+      // the fused OutConv one barrier from now
 #pragma unroll
       for (int pt = 0; pt < PT; ++pt) {
         const int m = wm * 128 + pt * 16 + p;                          // m & 15 == p
@@ -627,22 +670,19 @@ __global__ __launch_bounds__(THREADS, 1) void conv_ws64_kernel(ConvArgs a) {
       }
     }
     if (a.y_pool != nullptr) {
-      // MaxPool2d(2) (floor): the window's two rows are two of the wave's pixel tiles, its two columns adjacent lanes (one DPP swap)
+      // MaxPool2d(2) (floor): the window's two rows are two of the wave's pixel groups, its two columns (2 p, 2 p + 1) the same lane of the
+      // column-even and the column-odd group of a row: four accumulators of one lane, every lane stores a pooled pixel.  (max over the rows
+      // first, then over the columns, the even column's value first: the order of the DPP form this replaces)
       const int Ho = a.H / 2, Wo = a.W / 2;
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-        for (int pt = 0; pt < PT; ++pt) {
-          if ((pt >> 1) & 1) continue;                                 // odd patch rows are the windows' second rows
+        for (int r = 0; r < 4; r += 2) {                               // tile rows 4 wm + r, + 1
           f32x4 v;
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float t = fmaxf(acc[ct][pt][j], acc[ct][pt + 2][j]);
-            const float o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(t), 0xB1, 0xf, 0xf, true));      // quad_perm [1,0,3,2]
-            v[j] = fmaxf(t, o);
-          }
-          const int py = (ey0 + 4 * wm + (pt >> 1)) / 2, px = (ex0 + (pt & 1) * 16 + p) / 2;
-          if (!(p & 1) && py < Ho && px < Wo) {
+          for (int j = 0; j < 4; ++j) v[j] = fmaxf(fmaxf(acc[ct][r][j], acc[ct][r + 1][j]), fmaxf(acc[ct][4 + r][j], acc[ct][4 + r + 1][j]));
+          const int py = (ey0 + 4 * wm + r) / 2, px = ex0 / 2 + p;
+          if (py < Ho && px < Wo) {
             float* pp = a.y_pool + (((size_t)eb * Ho + py) * Wo + px) * a.Cout + n0 + wn * 32;       // this pixel's 32-channel chunk (128 bytes)
             if (a.y_pool_split) {
               // split layout: channels 16 ct + 4 g .. + 3 of the chunk = half (g & 1) of k-group 2 ct + (g >> 1): 8 bytes of hi, 8 of lo
@@ -674,6 +714,7 @@ bool conv_ws64_serves(const ConvArgs& a) {
   // it must still lie beyond the clip, never inside it
   if (4ull * a.H * a.W * a.C0 + 4ull * (a.W + 2) * (unsigned long long)a.C0 * 2ull >= 0xfffffff0ull ||
       4ull * a.H1 * a.W1 * a.C1 + 4ull * (a.W1 + 2) * (unsigned long long)a.C1 * 2ull >= 0xfffffff0ull) return false;
+  if (36ull * a.Cout * (unsigned long long)(a.C0 + a.C1) >= 0x7fffffffull) return false;    // the weight image's buffer descriptor and 32-bit block offsets
   if (c1 && (a.C0 != 64 || a.C1 != 0 || a.Cout != 64 || a.w1x1 != nullptr || !a.c1_w || !a.c1_scale || !a.c1_shift)) return false;
   const long long ntiles = (long long)((a.W + PW - 1) / PW) * ((a.H + PH - 1) / PH) * a.B;
   if (ntiles > 0x7fffffffLL / 2) return false;                         // (tile_of's round arithmetic stays inside 31 bits; conv_wd16_kernel takes those)

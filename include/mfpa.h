@@ -1371,6 +1371,66 @@ int mfpa_varidelay(const void* x, int x_f64, long long ldx, int B, long long T, 
 int mfpa_comb(const void* x, int x_f64, long long ldx, int B, long long T, const double* params, int params_per_row, long long max_delay,
               const unsigned char* apply, void* y, int y_f64, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Lossy coding (csrc/codec.hip): what a transform codec and a telephone channel do to a signal, along the rows of (B, T) samples.
+ * Neither is a bit stream: mfpa_transform_codec simulates transform coding (the rate is the high-resolution estimate
+ * 1/2 log2(variance / noise power) per coefficient, not an entropy-coded size), mfpa_mulaw is the G.711-style compander.  Additive
+ * to ABI 47.
+ *
+ * mfpa_transform_codec.  M = 256.  The row x[0..T) stands behind M zeros and before zeros; F = ceil(T / M) + 1 frames, frame f the
+ * padded samples [f M, f M + 512).  Float64 throughout, every product and sum of the allocation and the quantiser rounded on its own:
+ *   w[n]  = sin(pi (n + 1/2) / 512)
+ *   X[k]  = sum_{n < 512} w[n] x_f[n] cos(pi / M (n + 1/2 + M / 2) (k + 1/2)),  k < M          (the MDCT)
+ *   bands b < n_bands (<= MFPA_CODEC_MAX_BANDS) are [edges[b], edges[b + 1]), edges ascending from 0 to M, widths W_b
+ *   var_b = (sum_{k in b} X[k]^2) / W_b, summed in ascending k
+ *   m_b   = max over b' of var_b' * 10^(-a(b, b') / 10),  a = up_db (b - b') for b >= b' (a masker spreads upward), down_db (b' - b)
+ *           otherwise; the factor of b' = b is exactly 1, so m_b >= var_b; the factors are made on the host as pow(10, -(db * d) / 10)
+ *   L_b   = log2 var_b - log2 m_b   (<= 0);  bands with var_b = 0 are out
+ *   with R the row's bit budget per frame, for every band j that is in:
+ *     S_j = sum W_b,  P_j = sum W_b L_b  over {b in : L_b >= L_j} in ascending b;   lam_j = (P_j - 2 R) / S_j;   admissible if lam_j < L_j
+ *   lam   = lam_j of the admissible j with the smallest L_j (equal L_j: the same set, the same value); none admissible (R <= 0, a
+ *           silent frame, R NaN on the device): nothing is coded.  Reverse water-filling in closed form: lam is a continuous
+ *           function of the band energies, there is no iteration
+ *   band b is coded iff L_b > lam:  D_b = m_b * 2^lam,  step_b = sqrt(12 * D_b),  t = |X[k]| / step_b,  q = floor(t + 1/2),
+ *           Xq[k] = sign(X[k]) * q * step_b;  where t is not below 2^52 (the step is finer than a double resolves, or underflowed)
+ *           Xq[k] = X[k] and q counts as non-zero iff X[k] != 0.  Other bands: Xq[k] = 0 exactly.  q is never an index
+ *   y_f[n] = (2 / M) * (w[n] * sum_k Xq[k] cos(...)),  y[h M + i] = y_h[M + i] + y_{h+1}[i]: the earlier frame first
+ * R = +inf skips the allocation and the quantiser (Xq = X): y is x up to rounding (the TDAC identity).
+ *   x        (B, ldx) on the device, float32 (x_f64 = 0) or float64, ldx >= T; not overlapping y
+ *   rate     R of every row when row_rates is NULL;  row_rates: (B,) float64 on the device, R per row (not checked: the Python layer does)
+ *   band_edges  n_bands + 1 ints on the HOST, read before the launch
+ *   apply    NULL, or B bytes on the device: row b with apply[b] == 0 is copied through (bit for bit when y has x's type), its
+ *            lambda_out NaN and coded_out 0
+ *   y        (B, T) on the device, float32 (y_f64 = 0, the float64 value rounded once) or float64
+ *   lambda_out  NULL or (B, F) float64 on the device: lam per frame, NaN where nothing is coded, -inf with R = +inf
+ *   coded_out   NULL or (B, F) int32 on the device: the number of non-zero q of the frame, 0 with R = +inf
+ * A workgroup of four wavefronts owns MFPA_CODEC_FRAMES consecutive blocks of M outputs of one row and transforms the
+ * MFPA_CODEC_FRAMES + 1 frames that cover them, eight lanes per frame: the fold to 256 reals, a DCT-IV through a 128-point complex
+ * transform (the butterflies of csrc/mfpa_fft16.h), the allocation in the frame's lanes, the same DCT-IV back, and the overlap-add
+ * from LDS.  The frame two workgroups share is transformed by both.  No atomics, no work buffer; a row's bits do not depend on B,
+ * on the row's position or on the grid.
+ * MFPA_EINVAL before any launch, no device pointer dereferenced on the host: B < 1 or B > 65535, T < 1 or T > 2^30, ldx < T, x_f64 /
+ * y_f64 other than 0 or 1, n_bands outside [1, MFPA_CODEC_MAX_BANDS], a null x, y or band_edges, a misaligned pointer, edges that do
+ * not ascend strictly from 0 to 256, up_db or down_db negative or not finite, rate NaN with row_rates NULL. */
+#define MFPA_CODEC_FRAMES 31
+#define MFPA_CODEC_MAX_BANDS 32
+int mfpa_transform_codec(const void* x, int x_f64, long long ldx, int B, long long T, double rate, const double* row_rates,
+                         const int* band_edges, int n_bands, double up_db, double down_db, const unsigned char* apply, void* y, int y_f64,
+                         double* lambda_out, int* coded_out, void* stream);
+/* mfpa_mulaw.  mu = channels - 1, 2 <= channels <= 65536, float64, the formulas of torchaudio's mu_law_encoding / mu_law_decoding:
+ *   encode:  v = min(max(x, -1), 1);  c = sign(v) * log1p(mu * |v|) / log1p(mu);  code = floor((c + 1) / 2 * mu + 1/2)
+ *   decode:  v = 2 * code / mu - 1;   y = sign(v) * (exp(|v| * log1p(mu)) - 1) / mu
+ * log1p(mu) is the host's double.  mode MFPA_MULAW_ENCODE: x float32 / float64 -> y int32 (y_f64 = 0); MFPA_MULAW_DECODE: x int32
+ * (x_f64 = 0; any value, the code is a number and never an index) -> y float32 / float64; MFPA_MULAW_ROUNDTRIP: both in one pass, the
+ * code kept as a double.  apply (round trip only): NULL, or B bytes on the device, row b with apply[b] == 0 copied through.
+ * MFPA_EINVAL before any launch: B < 1 or B > 65535, T < 1 or T > 2^30, channels outside [2, 65536], an unknown mode, x_f64 / y_f64
+ * other than 0 or 1 or set on the int32 side, apply outside the round trip, a null or misaligned x or y. */
+#define MFPA_MULAW_ENCODE 0
+#define MFPA_MULAW_DECODE 1
+#define MFPA_MULAW_ROUNDTRIP 2
+int mfpa_mulaw(const void* x, int x_f64, int B, long long T, int channels, int mode, const unsigned char* apply, void* y, int y_f64,
+               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

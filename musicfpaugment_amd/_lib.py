@@ -230,6 +230,9 @@ _SIGNATURES = {
     "mfpa_varidelay": ([c_void_p, c_int, c_longlong, c_int, c_longlong, c_void_p, c_longlong, c_longlong, c_int, c_int, c_void_p, c_void_p,
                         c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
     "mfpa_comb": ([c_void_p, c_int, c_longlong, c_int, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_void_p], c_int),
+    "mfpa_transform_codec": ([c_void_p, c_int, c_longlong, c_int, c_longlong, c_double, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p,
+                              c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "mfpa_mulaw": ([c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p], c_int),
 }
 
 

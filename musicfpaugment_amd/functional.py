@@ -434,3 +434,54 @@ def wow_flutter(waveform: torch.Tensor, sample_rate, wow_hz: float = 0.8, wow_de
     return _on_rows(waveform, "wow_flutter", lambda rows: ops.variable_delay(
         rows, ops.speed_drift_delay(rows.shape[0], rows.shape[1], rate, [(wow_depth, wow_hz, phase[0]), (flutter_depth, flutter_hz, phase[1])],
                                     device=rows.device)))
+
+
+# ----------------------------------------------------------------------------- lossy coding (csrc/codec.hip)
+def transform_codec(waveform: torch.Tensor, sample_rate, kbps) -> torch.Tensor:
+    """A (..., T) float32 or float64 waveform through the simulated transform codec at `kbps` kbit/s (one number; math.inf is
+    lossless): ops.transform_codec(rows, kbps, sample_rate=sample_rate).  It simulates transform coding; parity with a real MP3,
+    AAC or GSM encoder is unpinned."""
+    rate = _rate(sample_rate)
+    if not isinstance(kbps, (int, float, np.integer, np.floating)) or math.isnan(kbps) or kbps == -math.inf:
+        raise ValueError(f"transform_codec: kbps must be one number, got {kbps!r}")
+    return _on_rows(waveform, "transform_codec", lambda rows: ops.transform_codec(rows, kbps, sample_rate=rate))
+
+
+def _channels(quantization_channels) -> int:
+    if not isinstance(quantization_channels, (int, np.integer)) or not 2 <= quantization_channels <= 65536:
+        raise ValueError(f"quantization_channels must be an integer in [2, 65536], got {quantization_channels!r}")
+    return int(quantization_channels)
+
+
+def mu_law_encoding(x: torch.Tensor, quantization_channels: int = 256) -> torch.Tensor:
+    """torchaudio.functional.mu_law_encoding on the device, in float64 (parity with torchaudio's float32 unpinned): a (..., T)
+    float32 or float64 tensor, clamped to [-1, 1], to int64 codes in [0, quantization_channels - 1]."""
+    ch = _channels(quantization_channels)
+    if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.dtype not in (torch.float32, torch.float64):
+        raise ValueError("x must be a float32 or float64 tensor (..., T)")
+    lead, T = x.shape[:-1], x.shape[-1]
+    g = x
+    if not g.is_cuda:
+        if not torch.cuda.is_available():
+            raise MfpaError("mu_law_encoding computes on the MI355X and none is present; no CPU fallback")
+        g = g.cuda()
+    with torch.cuda.device(g.device):
+        codes = ops.mu_law_encode(g.reshape(-1, T), ch)
+    return codes.reshape(*lead, T).to(torch.int64).to(x.device)
+
+
+def mu_law_decoding(x_mu: torch.Tensor, quantization_channels: int = 256) -> torch.Tensor:
+    """torchaudio.functional.mu_law_decoding on the device, in float64 rounded once to float32: a (..., T) integer tensor of codes
+    (int64 as mu_law_encoding returns them, or int32) to float32 samples in [-1, 1]."""
+    ch = _channels(quantization_channels)
+    if not isinstance(x_mu, torch.Tensor) or x_mu.dim() < 1 or x_mu.dtype not in (torch.int32, torch.int64):
+        raise ValueError("x_mu must be an int32 or int64 tensor (..., T)")
+    lead, T = x_mu.shape[:-1], x_mu.shape[-1]
+    g = x_mu
+    if not g.is_cuda:
+        if not torch.cuda.is_available():
+            raise MfpaError("mu_law_decoding computes on the MI355X and none is present; no CPU fallback")
+        g = g.cuda()
+    with torch.cuda.device(g.device):
+        y = ops.mu_law_decode(g.reshape(-1, T).to(torch.int32), ch)
+    return y.reshape(*lead, T).to(x_mu.device)

@@ -1431,6 +1431,43 @@ int mfpa_transform_codec(const void* x, int x_f64, long long ldx, int B, long lo
 int mfpa_mulaw(const void* x, int x_f64, int B, long long T, int channels, int mode, const unsigned char* apply, void* y, int y_f64,
                void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Model-free spectral noise suppression (csrc/denoise.hip): a windowed minimum-statistics noise tracker per frequency bin (Martin
+ * 2001, plain form), the decision-directed a-priori SNR (Ephraim and Malah 1984) and a Wiener gain on STFT magnitudes.  No weights.
+ * Additive to ABI 47.
+ *
+ * mfpa_spectral_suppress.  m[b][k][t] >= 0: (B, F, nF) magnitudes, frames contiguous (the layout of mfpa_stft_mag).  Float64
+ * throughout; every product, sum and quotient is rounded on its own, in the order written; max and min are fmax and fmin (they
+ * select and never round; a NaN operand loses).  Per clip b and bin k, all independent of each other:
+ *   p[t]  = m[t] * m[t]
+ *   s[0]  = p[0];   s[t] = alpha * s[t-1] + (1 - alpha) * p[t]                 (1 - alpha formed once, on the host)
+ *   n[t]  = bias * min{ s[u] : max(0, t - back) <= u <= min(nF - 1, t + ahead) }
+ *           or, when noise (B, F) is passed:  n[t] = noise[b][k]  (no bias, no tracker)
+ *   d[t]  = max(n[t], DBL_MIN)
+ *   q[t]  = p[t] / d[t]                                                        (may be +inf: digital silence inside the window)
+ *   i[t]  = max(q[t] - 1, 0)
+ *   xi[0] = max(a + (1 - a) * i[0], xi_min)
+ *   xi[t] = max(a * ((g[t-1] * g[t-1]) * q[t-1]) + (1 - a) * i[t], xi_min)
+ *   g[t]  = max(1 - 1 / (1 + xi[t]), g_floor)                                  (this form gives 1, not NaN, at xi = +inf)
+ *   y[t]  = g[t] * m[t]        or  (g[t] * m[t]) / denom[b]  when denom is passed
+ *   m        (B, F, nF) on the device, float32 (m_f64 = 0) or float64; not overlapping y
+ *   row_floor  NULL, or (B,) float64 on the device: g_floor per clip in place of the argument (not checked: the Python layer does)
+ *   noise    NULL, or (B, F) float64 on the device
+ *   denom    NULL, or (B,) float64 on the device
+ *   apply    NULL, or B bytes on the device: row b with apply[b] == 0 has g = 1 (y = m or m / denom[b]) and n = 0
+ *   y        (B, F, nF) on the device, float32 (y_f64 = 0, the float64 value rounded once) or float64
+ *   g_out, n_out   NULL, or (B, F, nF) float64 on the device: g and n
+ * One launch; a workgroup of one wavefront owns 16 bins of a clip, tiles of 16 bins x 64 frames go through LDS transposed, the gain
+ * walk lags the s walk by ceil(ahead / 64) tiles with s in a ring in LDS, the sliding minimum is taken by all lanes by block prefix
+ * and suffix minima.  No atomics, no work buffer; a row's bits do not depend on B, on the row's position or on the grid.
+ * MFPA_EINVAL before any launch, no device pointer dereferenced on the host: alpha or a outside [0, 1), xi_min <= 0 or not finite,
+ * g_floor outside [0, 1], bias <= 0 or not finite, back or ahead negative, back + ahead + 1 > MFPA_DENOISE_MAX_WINDOW, B, F or nF
+ * below 1, nF > 16384, B > 65535, F > 2^20, m_f64 / y_f64 other than 0 or 1, a null m or y, a misaligned pointer. */
+#define MFPA_DENOISE_MAX_WINDOW 128
+int mfpa_spectral_suppress(const void* m, int m_f64, int B, int F, int nF, double alpha, int back, int ahead, double bias, double a,
+                           double xi_min, double g_floor, const double* row_floor, const double* noise, const double* denom,
+                           const unsigned char* apply, void* y, int y_f64, double* g_out, double* n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

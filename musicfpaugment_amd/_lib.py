@@ -233,6 +233,8 @@ _SIGNATURES = {
     "mfpa_transform_codec": ([c_void_p, c_int, c_longlong, c_int, c_longlong, c_double, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p,
                               c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
     "mfpa_mulaw": ([c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p], c_int),
+    "mfpa_spectral_suppress": ([c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_double, c_double, c_double, c_double, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
 }
 
 

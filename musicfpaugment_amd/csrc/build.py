@@ -27,12 +27,14 @@ COMMON = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno
 # oracle's doubles (tests/_rir_oracle.py) only without contraction.  The compressor's recurrences (dynamics.hip) keep the order and the
 # roundings of the formula in include/mfpa.h, which tests/_dynamics_oracle.py restates.  The delay lines (delay.hip) likewise: the comb is
 # compared with tests/_delay_oracle.py bit for bit, and the fractional delay's staged and direct paths must round alike.  The transform codec (codec.hip) takes discrete decisions (a band coded
-# or not, a coefficient's rounding) from sums and products that tests/_codec_oracle.py restates in the order of include/mfpa.h.
+# or not, a coefficient's rounding) from sums and products that tests/_codec_oracle.py restates in the order of include/mfpa.h.  The spectral noise suppressor (denoise.hip) is two serial
+# recurrences of correctly rounded operations that tests/_denoise_oracle.py restates in numpy and compares bit for bit.
 PER_FILE = {
     "audfprint.hip": ["-ffp-contract=off"],
     "codec.hip": ["-ffp-contract=off"],
     "dejavu.hip": ["-ffp-contract=off"],
     "delay.hip": ["-ffp-contract=off"],
+    "denoise.hip": ["-ffp-contract=off"],
     "dynamics.hip": ["-ffp-contract=off"],
     "iir.hip": ["-ffp-contract=off"],
     "nplog.hip": ["-ffp-contract=off"],

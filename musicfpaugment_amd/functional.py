@@ -485,3 +485,16 @@ def mu_law_decoding(x_mu: torch.Tensor, quantization_channels: int = 256) -> tor
     with torch.cuda.device(g.device):
         y = ops.mu_law_decode(g.reshape(-1, T).to(torch.int32), ch)
     return y.reshape(*lead, T).to(x_mu.device)
+
+
+# ----------------------------------------------------------------------------- spectral noise suppression (csrc/denoise.hip)
+def spectral_denoise(waveform: torch.Tensor, sample_rate, **kw) -> torch.Tensor:
+    """A (..., T) float32 waveform through the model-free spectral suppressor: the pipeline's STFT (512 / 256, whatever the rate),
+    ops.spectral_suppress(mag, **kw) on its magnitudes, the inverse STFT on the input's phase -- denoisers.SpectralDenoiser's
+    denoise_waveform.  `kw`: alpha, back, ahead, bias, dd, xi_min_db, floor_db.  T must exceed 256."""
+    from .denoisers import SpectralDenoiser
+    _rate(sample_rate)
+    net = SpectralDenoiser(**kw)
+    if not isinstance(waveform, torch.Tensor) or waveform.dtype != torch.float32:
+        raise ValueError("waveform must be a float32 tensor (..., T)")
+    return _on_rows(waveform, "spectral_denoise", net.denoise_waveform)

@@ -1468,6 +1468,71 @@ int mfpa_spectral_suppress(const void* m, int m_f64, int B, int F, int nF, doubl
                            double xi_min, double g_floor, const double* row_floor, const double* noise, const double* denom,
                            const unsigned char* apply, void* y, int y_f64, double* g_out, double* n_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Programme loudness (csrc/loudness.hip): the meter of ITU-R BS.1770-4 / EBU R 128 with the loudness range of EBU Tech 3342 and a
+ * loudness-normalising gain.  Additive to ABI 47.  Rows are the channels of examples: (B, C, T) samples, R = B C rows.
+ *
+ * Geometry.  hop H samples (100 ms: H = floor(0.1 fs + 0.5), formed by the caller); segment k of a row is its samples
+ * [k H, (k + 1) H), nseg = T / H (integer division); a block is win consecutive segments and advances by one: nb = max(0, nseg - win
+ * + 1).  win = 4 is the 400 ms block with 75 % overlap of BS.1770, win = 30 the 3 s short-term window.  The trailing T - nseg H
+ * samples are filtered and count for the peak but belong to no segment.
+ *
+ * mfpa_loudness_segments.  y = the row filtered by the S second-order sections sos (S, 6), shared by all rows, float64 on the device,
+ * a0 == 1 and not read, zero initial state: mfpa_sosfilt's arithmetic, order and chunking, so y is mfpa_sosfilt's float64 output bit
+ * for bit before its rounding to the sample type.  S == 0: y = x (a plain mean-square meter).  y is not stored.
+ *   seg[r][k] = sum of y[n]^2 over segment k, float64, in THIS order.  Sample n belongs to lane group n / 16 (16 consecutive samples),
+ *   to lane l = (n / 16) mod 64 and to super-chunk n / 1024 (64 lane groups).
+ *     t   = the 16 squares of a lane group, those outside the segment replaced by 0, added by the pairwise tree: neighbours first
+ *           (s_0 + s_1, s_2 + s_3, ...), then pairs of pairs, four levels
+ *     a_l = a_l + t for the lane groups of lane l, one per super-chunk that overlaps the segment, in increasing n; a_l starts at 0
+ *     seg = the 64 a_l combined by the binary tree over l: neighbours first (a_0 + a_1, a_2 + a_3, ...), then pairs of pairs, six levels
+ *   peak[r] = max |x[n]| over all T samples of the UNFILTERED input, exact, as float64; a NaN sample is skipped (fmax).  NULL: not
+ *   wanted.
+ *   x (R, T) float32 (x_f64 = 0) or float64 on the device; seg (R, nseg) float64 (may be NULL when nseg == 0); work: work_len >=
+ *   mfpa_loudness_work(S) float64 on the device (the powers table of mfpa_sosfilt; may be NULL when S == 0).
+ * One wavefront owns a row; no atomics, no work buffer but the powers; a row's bits do not depend on R, on its position or on the grid.
+ * MFPA_EINVAL before any launch, no pointer dereferenced on the host: R < 0 or R > 65535, T < 1 or T > 2^30, S < 0 or S >
+ * MFPA_SOS_MAX_SECTIONS, hop < 1 or hop > 2^24, x_f64 other than 0 or 1, work_len too short, and with R > 0 a null x, a null seg with
+ * nseg > 0, a null sos or work with S > 0, a misaligned pointer.  R == 0: MFPA_OK, no launch.
+ *
+ * mfpa_loudness_gate, per example b, from seg (B, C, nseg):
+ *   p[j] = sum over c of  G[c] * ((seg[c][j] + seg[c][j+1] + ... + seg[c][j+win-1]) / d),   d = (double)win * (double)hop
+ *          (k increasing inside the block from seg[c][j], then c increasing from the term of c = 0; G = weights (C,) float64 on the
+ *          device, NULL: 1 for every channel; BS.1770 gives the surround pair 1.41)
+ *   absolute gate:  A = { j : p[j] > p_abs },  n_abs = |A|,  m_abs = sum(p over A) / n_abs  (0 when n_abs == 0)
+ *   relative gate:  G2 = { j in A : p[j] > rel * m_abs },  n_rel = |G2|,  P_gated = sum(p over G2) / n_rel  (0 when n_rel == 0)
+ *   A NaN power fails every comparison.  Both sums have this order: t = j mod 256 collects its members in increasing j into a
+ *   partial sum that starts at 0; the 256 partial sums a_t are combined by a_t = a_t + a_(t + off) for t < off, off = 128, 64, ..., 1.
+ *   The host passes p_abs = 10^((-70 + 0.691) / 10) and rel = 0.1 (integrated loudness) or 0.01 (range); there is no logarithm here.
+ *   power (B, 2) float64: P_gated, m_abs.  counts (B, 2) int32: n_abs, n_rel.
+ *   blocks  NULL, or (B, nb) float64: p (the momentary curve at win = 4, the short-term curve at win = 30)
+ *   range   NULL, or (B, 2) float64: the values at ranks (n + 4) / 10 and (19 n - 9) / 20 (integer divisions, n = n_rel) of the
+ *           ascending members of G2: the nearest ranks at 10 % and 95 %; 0 and 0 when n == 0.  nb <= MFPA_LOUDNESS_MAX_RANGE_BLOCKS.
+ * LUFS = -0.691 + 10 log10(P) and LRA = 10 log10(P_hi / P_lo) are formed by the caller.
+ * MFPA_EINVAL before any launch: B < 0 or B > 65535, C < 1 or C > MFPA_LOUDNESS_MAX_CHANNELS, nseg < 0 or nseg > 2^30, hop < 1 or hop >
+ * 2^24, win < 1 or win > MFPA_LOUDNESS_MAX_WINDOW, p_abs or rel negative or not finite, range with nb > MFPA_LOUDNESS_MAX_RANGE_BLOCKS,
+ * and with B > 0 a null power or counts, a null seg with nseg > 0, a misaligned pointer.  B == 0: MFPA_OK, no launch.
+ *
+ * mfpa_loudness_apply.  g[b] = sqrt(target[b] / gated[b]), both correctly rounded; target (B,) float64 holds P_target = 10^((LUFS
+ * target + 0.691) / 10) from the host, gated (B,) float64 is P_gated (stride 1: copy it out of `power`).  With peak_limit > 0 and peak
+ * (B, C): g = min(g, peak_limit / max_c peak[b][c]).  y = x g in float64, rounded once for float32.  A row is copied bit for bit when
+ * gated[b] == 0, when g is not finite, or when apply[b] == 0 (apply NULL or B bytes).  gain: NULL, or (B,) float64: g, 1 for a copied
+ * example.  Everything is read on the device: the chain segments -> gate -> apply needs no host synchronisation.
+ * MFPA_EINVAL before any launch: B < 0, C < 1 or C > MFPA_LOUDNESS_MAX_CHANNELS, B C > 65535, T < 1 or T > 2^30, x_f64 other than 0 or
+ * 1, peak_limit negative or not finite, peak_limit > 0 without peak or peak with peak_limit == 0, and with B > 0 a null x, y, gated
+ * or target, a misaligned pointer.  B == 0: MFPA_OK, no launch. */
+#define MFPA_LOUDNESS_MAX_CHANNELS 8
+#define MFPA_LOUDNESS_MAX_WINDOW 64
+#define MFPA_LOUDNESS_MAX_RANGE_BLOCKS 16384
+int mfpa_loudness_segments(const void* x, int x_f64, int R, long long T, const double* sos, int S, int hop, double* work, long long work_len,
+                           double* seg, double* peak, void* stream);
+/* HOST function, no GPU work: *work_len = S * 256 doubles.  MFPA_EINVAL: a null pointer, S < 0 or S > MFPA_SOS_MAX_SECTIONS. */
+int mfpa_loudness_work(int S, long long* work_len);
+int mfpa_loudness_gate(const double* seg, int B, int C, long long nseg, int hop, int win, const double* weights, double p_abs, double rel,
+                       double* power, int* counts, double* blocks, double* range, void* stream);
+int mfpa_loudness_apply(const void* x, int x_f64, int B, int C, long long T, const double* gated, const double* target, const double* peak,
+                        double peak_limit, const unsigned char* apply, void* y, double* gain, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

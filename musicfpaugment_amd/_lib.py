@@ -235,6 +235,13 @@ _SIGNATURES = {
     "mfpa_mulaw": ([c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p], c_int),
     "mfpa_spectral_suppress": ([c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_double, c_double, c_double, c_double, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "mfpa_loudness_segments": ([c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p],
+                               c_int),
+    "mfpa_loudness_work": ([c_int, c_void_p], c_int),
+    "mfpa_loudness_gate": ([c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p], c_int),
+    "mfpa_loudness_apply": ([c_void_p, c_int, c_int, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
+                             c_void_p], c_int),
 }
 
 

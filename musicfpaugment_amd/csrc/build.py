@@ -28,7 +28,9 @@ COMMON = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-Wall", "-Wno
 # roundings of the formula in include/mfpa.h, which tests/_dynamics_oracle.py restates.  The delay lines (delay.hip) likewise: the comb is
 # compared with tests/_delay_oracle.py bit for bit, and the fractional delay's staged and direct paths must round alike.  The transform codec (codec.hip) takes discrete decisions (a band coded
 # or not, a coefficient's rounding) from sums and products that tests/_codec_oracle.py restates in the order of include/mfpa.h.  The spectral noise suppressor (denoise.hip) is two serial
-# recurrences of correctly rounded operations that tests/_denoise_oracle.py restates in numpy and compares bit for bit.
+# recurrences of correctly rounded operations that tests/_denoise_oracle.py restates in numpy and compares bit for bit.  The loudness meter
+# (loudness.hip) runs the IIR recurrence of iir.hip (mfpa_sos.h) and sums squares and block powers in the order of include/mfpa.h, which
+# tests/_loudness_oracle.py restates bit for bit.
 PER_FILE = {
     "audfprint.hip": ["-ffp-contract=off"],
     "codec.hip": ["-ffp-contract=off"],
@@ -37,6 +39,7 @@ PER_FILE = {
     "denoise.hip": ["-ffp-contract=off"],
     "dynamics.hip": ["-ffp-contract=off"],
     "iir.hip": ["-ffp-contract=off"],
+    "loudness.hip": ["-ffp-contract=off"],
     "nplog.hip": ["-ffp-contract=off"],
     "rir.hip": ["-ffp-contract=off"],
 }

@@ -34,48 +34,13 @@
 // for 256 rows: DESIGN.md section 3.15).  The next super-chunk's loads are issued before the sections of the current one run and land
 // in LDS before the current one's stores are issued.  Each lane's own power M^l of every section sits in LDS too (25 KB per row with
 // the tile, hence two rows per workgroup).  One wavefront per row: splitting a row over the waves of a workgroup was not built.
-#include "mfpa_common.h"
+#include "mfpa_sos.h"
 
+// The geometry (L, SUPER, LDS_STRIDE, POWER_DOUBLES), sos_powers_kernel and one section's pass (sos_section) live in mfpa_sos.h, which
+// loudness.hip shares.
 namespace {
 
 constexpr int ROWS_PER_BLOCK = 2;
-constexpr int L = 16;                                    // samples per lane
-constexpr int SUPER = MFPA_WAVE * L;                     // samples per super-chunk
-constexpr int LDS_STRIDE = L + 1;                        // doubles per lane in LDS
-constexpr int SCAN_STEPS = 6;                            // offsets 2^k, k < 6: 64 lanes
-constexpr int POWER_DOUBLES = MFPA_WAVE * 4;             // per section: m00 m01 m10 m11 of M^j, j = 1..64, at 4 (j - 1)
-
-__device__ __forceinline__ int lds_slot(int p) { return (p >> 4) * LDS_STRIDE + (p & (L - 1)); }
-
-// LDS written by one lane and read by another lane of the SAME wavefront: the hardware keeps a wavefront's LDS operations in order,
-// the fences keep the compiler from moving them across.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Thread t = (row r, section s, unit state u): the homogeneous recurrence from e_u; the state after 16 j steps is column u of
-// A^(16 j).  z1 <- z2 - a1 y is (b1 0 - a1 y) + z2 of the filter with the zero products left out (the same double).
-__global__ void sos_powers_kernel(const double* __restrict__ sos, int n, double* __restrict__ work) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int u = t & 1;
-  const double* c = sos + (size_t)(t >> 1) * 6;
-  const double a1 = c[4], a2 = c[5];
-  double z1 = u ? 0.0 : 1.0, z2 = u ? 1.0 : 0.0;
-  double* out = work + (size_t)(t >> 1) * POWER_DOUBLES + u;
-  for (int i = 1; i <= SUPER; ++i) {
-    const double y = z1;
-    z1 = z2 - a1 * y;
-    z2 = -(a2 * y);
-    if ((i & (L - 1)) == 0) {
-      const int j = i / L - 1;
-      out[4 * j] = z1;
-      out[4 * j + 2] = z2;
-    }
-  }
-}
 
 template <typename T>
 __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void sosfilt_kernel(const T* __restrict__ x, int B, long long n, const double* __restrict__ sos,
@@ -144,43 +109,9 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void sosfilt_kernel(const T* _
     const int tail_lane = tail >> 4, tail_i = tail & (L - 1);
 
     for (int s = 0; s < S; ++s) {
-      const double b0 = coef[s * 6], b1 = coef[s * 6 + 1], b2 = coef[s * 6 + 2], a1 = coef[s * 6 + 4], a2 = coef[s * 6 + 5];
-      const double* m = pw + s * POWER_DOUBLES;
-      double z1 = 0.0, z2 = 0.0;
-#pragma unroll
-      for (int i = 0; i < L; ++i) {
-        const double o = b0 * v[i] + z1;
-        z1 = (b1 * v[i] - a1 * o) + z2;
-        z2 = b2 * v[i] - a2 * o;
-      }
-#pragma unroll
-      for (int k = 0; k < SCAN_STEPS; ++k) {
-        const double* q = m + 4 * ((1 << k) - 1);
-        const double t1 = __shfl_up(z1, 1 << k), t2 = __shfl_up(z2, 1 << k);
-        if (lane >= (1 << k)) {
-          z1 = z1 + (q[0] * t1 + q[1] * t2);
-          z2 = z2 + (q[2] * t1 + q[3] * t2);
-        }
-      }
       const double k1 = __shfl(c1, s), k2 = __shfl(c2, s);
-      const double* q = own_powers + s * MFPA_WAVE * 4;   // M^lane
-      const double p1 = __shfl_up(z1, 1), p2 = __shfl_up(z2, 1);
-      z1 = lane ? (q[0] * k1 + q[1] * k2) + p1 : k1;
-      z2 = lane ? (q[2] * k1 + q[3] * k2) + p2 : k2;
-      double f1 = 0.0, f2 = 0.0;
-#pragma unroll
-      for (int i = 0; i < L; ++i) {
-        const double o = b0 * v[i] + z1;
-        z1 = (b1 * v[i] - a1 * o) + z2;
-        z2 = b2 * v[i] - a2 * o;
-        v[i] = o;
-        if (i == tail_i) {
-          f1 = z1;
-          f2 = z2;
-        }
-      }
-      f1 = __shfl(f1, tail_lane);
-      f2 = __shfl(f2, tail_lane);
+      double f1, f2;
+      sos_section(v, coef + s * 6, pw + s * POWER_DOUBLES, own_powers + s * MFPA_WAVE * 4, k1, k2, lane, tail_lane, tail_i, f1, f2);
       if (lane == s) {
         c1 = f1;
         c2 = f2;

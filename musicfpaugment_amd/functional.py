@@ -498,3 +498,78 @@ def spectral_denoise(waveform: torch.Tensor, sample_rate, **kw) -> torch.Tensor:
     if not isinstance(waveform, torch.Tensor) or waveform.dtype != torch.float32:
         raise ValueError("waveform must be a float32 tensor (..., T)")
     return _on_rows(waveform, "spectral_denoise", net.denoise_waveform)
+
+
+# ----------------------------------------------------------------------------- programme loudness (csrc/loudness.hip)
+K_WEIGHTING_DESIGNS = ("bs1770", "torchaudio")
+
+
+def _k_stage(sample_rate: float, f0: float, Q: float):
+    K = math.tan(math.pi * f0 / sample_rate)
+    return K, 1.0 + K / Q + K * K
+
+
+def k_weighting_sos(sample_rate, design: str = "bs1770") -> np.ndarray:
+    """(2, 6) float64, a0 == 1: the K-weighting of ITU-R BS.1770 as two second-order sections, the shelf and the high-pass, at any
+    rate; host arithmetic.
+      "bs1770"      the analogue prototypes behind the standard's 48 kHz table, bilinear-transformed at `sample_rate` (the
+                    re-derivation open-source meters use); at 48 kHz it gives the table to 9e-16;
+      "torchaudio"  torchaudio.functional.loudness' own pair: a cookbook high shelf (1500 Hz, Q 1/sqrt 2, +4 dB) and high-pass (38 Hz,
+                    Q 0.5).  Up to 0.043 dB from the table at 48 kHz and 0.18 dB low at 997 Hz at 8 kHz, so it is not the default;
+                    parity with torchaudio itself is unpinned."""
+    fs = _rate(sample_rate)
+    if design not in K_WEIGHTING_DESIGNS:
+        raise ValueError(f"design must be one of {K_WEIGHTING_DESIGNS}, got {design!r}")
+    if design == "torchaudio":
+        return ops.sos_normalized(np.stack([biquad_coefficients("highshelf", fs, 1500.0, 1.0 / math.sqrt(2.0), 4.0),
+                                            biquad_coefficients("highpass", fs, 38.0, 0.5)]))
+    if fs <= 2.0 * 1681.974450955533:
+        raise ValueError(f"the K-weighting shelf sits at 1682 Hz: sample_rate must exceed 3364 Hz, got {sample_rate}")
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K, a0 = _k_stage(fs, f0, Q)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    shelf = [(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0, 1.0, 2.0 * (K * K - 1.0) / a0,
+             (1.0 - K / Q + K * K) / a0]
+    Q = 0.5003270373238773
+    K, a0 = _k_stage(fs, 38.13547087602444, Q)
+    highpass = [1.0, -2.0, 1.0, 1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    return np.array([shelf, highpass], dtype=np.float64)
+
+
+def _on_examples(waveform: torch.Tensor, who: str, run):
+    """run(x (N, C, T) on the GPU) for a (..., C, T) waveform on any device -> (tensor on the GPU, lead shape, the input's device)."""
+    if not isinstance(waveform, torch.Tensor) or waveform.dim() < 2 or waveform.dtype not in (torch.float32, torch.float64):
+        raise ValueError("waveform must be a float32 or float64 tensor (..., channels, T)")
+    x = waveform
+    if not x.is_cuda:
+        if not torch.cuda.is_available():
+            raise MfpaError(f"{who} computes on the MI355X and none is present; no CPU fallback")
+        x = x.cuda()
+    with torch.cuda.device(x.device):
+        return run(x.reshape(-1, *x.shape[-2:]))
+
+
+def loudness(waveform: torch.Tensor, sample_rate: int) -> torch.Tensor:
+    """torchaudio.functional.loudness: integrated loudness (ITU-R BS.1770-4) of (..., channels, T) -> (...) float64 LUFS, on the
+    input's device.  Every channel has weight 1 and the K-weighting is k_weighting_sos(sample_rate, "bs1770"), not torchaudio's pair
+    (ops.loudness takes weights and the design)."""
+    _rate(sample_rate)
+    out = _on_examples(waveform, "loudness", lambda x: ops.loudness(x, sample_rate))
+    return out.reshape(waveform.shape[:-2]).to(waveform.device)
+
+
+def loudness_range(waveform: torch.Tensor, sample_rate: int) -> torch.Tensor:
+    """Loudness range (EBU Tech 3342) of (..., channels, T) -> (...) float64 LU (ops.loudness_range)."""
+    _rate(sample_rate)
+    out = _on_examples(waveform, "loudness_range", lambda x: ops.loudness_range(x, sample_rate))
+    return out.reshape(waveform.shape[:-2]).to(waveform.device)
+
+
+def loudness_normalize(waveform: torch.Tensor, sample_rate: int, target_lufs: float, peak_limit: Optional[float] = None) -> torch.Tensor:
+    """(..., channels, T) with every example scaled to `target_lufs` integrated loudness (ops.loudness_normalize), same shape, dtype and
+    device.  Silence comes back unchanged."""
+    _rate(sample_rate)
+    _numbers("loudness_normalize", target_lufs=target_lufs)
+    out = _on_examples(waveform, "loudness_normalize", lambda x: ops.loudness_normalize(x, sample_rate, float(target_lufs), peak_limit=peak_limit))
+    return out.reshape(waveform.shape).to(waveform.device)

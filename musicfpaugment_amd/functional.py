@@ -32,6 +32,7 @@ import torch
 
 from . import ops
 from ._lib import MfpaError
+from .ops._args import _host_f64, _sample_rate as _rate
 
 BIQUAD_KINDS = ("lowpass", "highpass", "bandpass", "bandpass_skirt", "bandreject", "allpass", "peaking", "lowshelf", "highshelf")
 
@@ -101,7 +102,7 @@ def _filter(waveform: torch.Tensor, sos: np.ndarray, clamp: bool, who: str) -> t
 
 
 def _coeff_rows(c, name: str) -> np.ndarray:
-    c = np.array(c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c, dtype=np.float64)
+    c = np.array(_host_f64(c, name))
     if c.ndim not in (1, 2) or c.shape[-1] < 1:
         raise ValueError(f"{name} must be (num_order + 1,) or (num_filters, num_order + 1), got {c.shape}")
     return c
@@ -180,7 +181,7 @@ def treble_biquad(waveform: torch.Tensor, sample_rate: int, gain: float, central
 
 # ----------------------------------------------------------------------------- room impulse responses (csrc/rir.hip)
 def _rooms(room) -> np.ndarray:
-    room = np.asarray(room.detach().cpu().numpy() if isinstance(room, torch.Tensor) else room, dtype=np.float64)
+    room = _host_f64(room, "room")
     if room.ndim not in (1, 2) or room.shape[-1] != 3:
         raise ValueError(f"room must be (3,) or (B, 3), got {room.shape}")
     if not (np.all(np.isfinite(room)) and np.all(room > 0.0)):
@@ -239,8 +240,8 @@ def compressor_params(sample_rate, threshold_db=-20.0, ratio=4.0, attack_ms=5.0,
     N (the others are repeated).  slope = 1 - 1 / ratio (ratio >= 1, float("inf") is a limiter), the coefficients are
     ops.time_coef(ms / 1000, sample_rate).  Host arithmetic.  ValueError: a ratio below 1 or NaN, a negative knee or time, a value
     that is not finite, lengths that do not agree."""
-    vals = [np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
-            for v in (threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db)]
+    vals = [_host_f64(v, n) for v, n in ((threshold_db, "threshold_db"), (ratio, "ratio"), (knee_db, "knee_db"), (attack_ms, "attack_ms"),
+                                         (release_ms, "release_ms"), (makeup_db, "makeup_db"))]
     if any(v.ndim > 1 for v in vals):
         raise ValueError("every compressor parameter must be a number or have one entry per row")
     try:
@@ -287,13 +288,6 @@ def limiter(waveform: torch.Tensor, sample_rate: int, threshold_db=-1.0, release
 
 
 # ----------------------------------------------------------------------------- delay-line effects (csrc/delay.hip)
-def _rate(sample_rate) -> float:
-    rate = float(sample_rate)
-    if not (math.isfinite(rate) and rate > 0.0):
-        raise ValueError(f"sample_rate must be positive, got {sample_rate}")
-    return rate
-
-
 def _numbers(who: str, **values) -> None:
     """Each value one finite real number, a Python or numpy scalar."""
     for name, v in values.items():
